@@ -12,11 +12,16 @@ by all ranks per second of that combined step ("Text2Mel+SSRN").  
 HBM before the timed region.  Weak scaling: the per-GPU batch is fixed, gradients are averaged with a
 flat RCCL all-reduce per step.
 
-Rank 0 prints ONE JSON line with the driver's contract plus:
+Rank 0 prints ONE JSON line with the driver's contract (metric, value, unit, higher_is_better, dtype, ms_per_step = milliseconds of
+one timed step).  A plain run does only that: set up, warm up, time the K steps, write --dump-outputs if given, print the line.
+With --full the line also holds (each leg can be dropped with its --no-* option):
+  config.*_ms, *_fps  each model's step timed on its own, the WGAN-GP cycle, the other arithmetic modes, the eager HIP step
   roofline            the dominant kernel (dilated Conv1d implicit GEMM, split-fp16 MFMA) timed with HIP events here
-  cpu_baseline        the CPU oracle (same stock-op sequence the reference runs) on a bounded sample
+  cpu_baseline        the CPU oracle (same stock-op sequence the reference runs) on a bounded sample, and the losses of the timed
+                      trainers' first iterations checked against it
   stock_gpu_baseline  the same op sequence on torch's stock GPU kernels (MIOpen / rocBLAS), fp32, eager: the path the reference
                       itself would take on this GPU (SURVEY.md "facts"); config.eager_ms_per_step = the HIP path without hipGraphs
+  config.ge2e_*       BASELINE config 5 (GE2E speaker embedder)
 """
 import argparse
 import json
@@ -43,6 +48,12 @@ def parse():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--no-graph", action="store_true", help="launch eagerly instead of replaying a captured hipGraph")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run the legs below (per-model split, adversarial cycle, other arithmetic modes, eager and stock-op "
+                         "timings, roofline, GE2E, CPU baseline and the parity checks against the CPU oracle); a plain run times the headline step only")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed (loss terms, attention, a fixed sample of the updated "
+                         "parameters) as DIR/<name>.npy in float32")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-adversarial", action="store_true", help="skip the extra WGAN-GP cycle timing")
     ap.add_argument("--no-fp32", action="store_true", help="skip the exact-fp32 timing of the same step")
@@ -52,7 +63,7 @@ def parse():
     ap.add_argument("--ge2e", action="store_true", help="measure BASELINE config 5 (GE2E speaker embedder) instead and print its JSON line")
     ap.add_argument("--batch", type=int, default=B_PER_GPU)
     ap.add_argument("--check-replicas", action="store_true",
-                    help="N > 1: after the timed steps (and the adversarial cycles) all-gather a checksum of every model's parameters and fail unless all ranks hold the same replica")
+                    help="N > 1: after the timed steps (and, with --full, the adversarial cycles) all-gather a checksum of every model's parameters and fail unless all ranks hold the same replica")
     ap.add_argument("--launch-check", action="store_true",
                     help="rehearse ONLY the launch plumbing of --gpus N, without any kernel launch or device memory (device COUNTING may initialise the HIP runtime): N ranks, gloo rendezvous on 127.0.0.1, local-rank folding, "
                          "one all-gather, ONE JSON line from rank 0, non-zero exit if any rank dies (runs on a GPU-less host)")
@@ -106,6 +117,31 @@ class Trainer:
     def first_losses(self):
         """Loss terms of optimizer iterations 0 and 1 (initial weights; after one Adam step) as lists of floats."""
         return [[float(v) for v in t.cpu()] for t in self.stepper.loss_log[:2]]
+
+
+DUMP_PARAM_SAMPLE, DUMP_SEED = 1 << 22, 0     # 16 MB of each model's 24.1 M (Text2Mel) / 7.0 M (SSRN) updated parameters
+
+
+def dump_outputs(path, trainers):
+    """``--dump-outputs DIR``: what the last timed step handed back, per trainer -- ``<kind>_losses`` (the loss terms ``TrainStep``
+    returns), ``text2mel_attention`` (B x N x T) and ``<kind>_params_sample``: the updated parameters concatenated in
+    ``model.parameters()`` order, at DUMP_PARAM_SAMPLE positions drawn once from a generator seeded with DUMP_SEED (the same positions in
+    every run).  float32, ~41 MB in all at B = 32."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for tr in trainers:
+        st = tr.stepper
+        arrays = {"losses": torch.stack([o.reshape(()) for o in st.out])}
+        if st.att is not None:
+            arrays["attention"] = st.att
+        with torch.no_grad():
+            flat = torch.cat([p.detach().reshape(-1) for p in tr.model.parameters()])
+            if flat.numel() > DUMP_PARAM_SAMPLE:
+                pick = np.sort(np.random.default_rng(DUMP_SEED).choice(flat.numel(), DUMP_PARAM_SAMPLE, replace=False))
+                flat = flat[torch.from_numpy(pick).to(flat.device)]
+        arrays["params_sample"] = flat
+        for name, a in arrays.items():
+            np.save(os.path.join(path, "%s_%s.npy" % (tr.kind, name)), a.detach().float().cpu().numpy())
 
 
 def adversarial_cycle_ms(kind, batch, dev, world=1, cycles=3, check_replicas=False):
@@ -755,6 +791,8 @@ def main():
         return
     if args.gpus < 1:
         raise SystemExit("bench: --gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("bench: --steps must be >= 1 and --warmup >= 0")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(launch_ranks(args.gpus))
     if args.launch_check:
@@ -830,7 +868,10 @@ def main():
     ssr.prepare()
     # one "step" of the benchmark: a Text2Mel iteration and an SSRN iteration (independent models), back to back
     per_step = timed([t2m, ssr], args.steps, args.warmup)
-    split = {"text2mel": timed([t2m], args.steps, 0), "ssrn": timed([ssr], args.steps, 0)}      # per model, not part of `value`
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, [t2m, ssr])
+    if args.full:
+        split = {"text2mel": timed([t2m], args.steps, 0), "ssrn": timed([ssr], args.steps, 0)}      # per model, not part of `value`
     frames_per_step = args.batch * T_MEL * world
     loss_t2m, loss_ssrn = t2m.loss, ssr.loss
     replicas_equal = None
@@ -859,16 +900,16 @@ def main():
                                   "batch %d utterances/GPU, N=186, T=325, 80 mel -> 513x1300 linear, hidden 256, random-init" % args.batch,
                       "global_batch": args.batch * world, "parallelism": "dp%d" % world,
                       "launch": "hipGraph replay" if use_graph else "eager", "ddp": ddp_note,
-                      "text2mel_ms": round(split["text2mel"] * 1e3, 3), "ssrn_ms": round(split["ssrn"] * 1e3, 3),
-                      "text2mel_fps": round(frames_per_step / split["text2mel"], 1),
-                      "ssrn_fps": round(frames_per_step / split["ssrn"], 1),
                       "final_loss_text2mel": round(loss_t2m, 5), "final_loss_ssrn": round(loss_ssrn, 5)}}
     cfg = res["config"]          # scalars only: the driver's parser keeps flat keys
+    if args.full:
+        cfg.update({"text2mel_ms": round(split["text2mel"] * 1e3, 3), "ssrn_ms": round(split["ssrn"] * 1e3, 3),
+                    "text2mel_fps": round(frames_per_step / split["text2mel"], 1), "ssrn_fps": round(frames_per_step / split["ssrn"], 1)})
     if replicas_equal is not None:
         cfg["replica_checksums_equal"] = True       # (a difference is a non-zero exit, never a false on the line); adversarial models are checked below
     del t2m, ssr
     torch.cuda.empty_cache()
-    if not args.no_adversarial:
+    if args.full and not args.no_adversarial:
         # BASELINE config 3 (--adversarial; config 4 when N > 1): reported beside the headline, never inside `value`
         a1 = adversarial_cycle_ms("text2mel", args.batch, dev, world, check_replicas=args.check_replicas)
         a2 = adversarial_cycle_ms("ssrn", args.batch, dev, world, check_replicas=args.check_replicas)
@@ -879,9 +920,9 @@ def main():
                                         "hipGraph replay" + ("; data parallel: global adaptive weight, bucketed generator all-reduce, packed critic all-reduce" if world > 1 else "")})
         torch.cuda.empty_cache()
     adv_first = None
-    if world == 1 and not args.no_adversarial and not args.no_cpu_baseline and args.batch == B_PER_GPU:
+    if args.full and world == 1 and not args.no_adversarial and not args.no_cpu_baseline and args.batch == B_PER_GPU:
         adv_first = {k: adversarial_first_g_iterations(k, args.batch, dev) for k in ("text2mel", "ssrn")}
-    if world == 1 and not args.no_fp32:
+    if args.full and world == 1 and not args.no_fp32:
         # the same step in the other arithmetic modes, beside the headline and never inside `value`: exact fp32 MFMA
         # (v_mfma_f32_16x16x4_f32: what strict fp32 fma chains cost) and, opt-in for users who accept ~2^-16 products, split-bf16
         for other, key in (("fp32", "fp32_exact"), ("bf16x3", "fast_bf16x3"), ("f16x2", "f16x2")):
@@ -895,7 +936,7 @@ def main():
             del f1, f2
             torch.cuda.empty_cache()
         spoofsv_amd.set_precision(args.precision)
-    if world == 1 and not args.no_stock:
+    if args.full and world == 1 and not args.no_stock:
         # the same HIP step launched EAGERLY (what a ragged real-data run gets: harness.ordinary_train captures only fixed shapes) ...
         if use_graph:
             e1, e2 = Trainer("text2mel", args.batch, dev, rank, world, False), Trainer("ssrn", args.batch, dev, rank, world, False)
@@ -913,9 +954,9 @@ def main():
             e = max(abs(a - b) / max(abs(b), 1e-12) for a, b in zip(first[kind][0], stock_first[kind]))
             cfg["loss_rel_err_vs_stock_gpu_%s_iter0" % kind] = float("%.3g" % e)
     if rank == 0:
-        if not args.no_roofline:
+        if args.full and not args.no_roofline:
             res["roofline"] = kernel_roofline(dev)
-        if world == 1 and not args.no_ge2e:
+        if args.full and world == 1 and not args.no_ge2e:
             # BASELINE config 5 on the same line (flat scalars); `python bench.py --ge2e` prints the full record
             g = ge2e_config5()
             cfg.update({"ge2e_utt_per_s": g["value"], "ge2e_ms": g["ms"], "ge2e_tflops": g["tflops"], "ge2e_rel_err_vs_oracle": g["rel_err_vs_cpu_oracle"],
@@ -924,7 +965,7 @@ def main():
                         "ge2e_train_iteration_ms": g["train_iteration"]["ms"], "ge2e_cpu_utt_per_s": g["cpu_baseline"]["value"],
                         "ge2e_cpu_cores": g["cpu_baseline"]["cores"]})
         bad = None
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             res["cpu_baseline"] = cpu_baseline()
             cfg["speedup_vs_cpu_baseline"] = round(res["value"] / res["cpu_baseline"]["value"], 1)
             # Parity of the configuration that was just timed: the oracle ran the SAME model (seed 1234) on the SAME batch

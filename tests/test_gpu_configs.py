@@ -123,3 +123,39 @@ def test_config3_adversarial_critic_iteration_at_batch_32_vs_oracle(kind):
         want = dsd[n].grad
         e = float((p.grad.detach().cpu() - want).norm() / max(1e-6, float(want.norm())))
         assert e < 3e-3, (kind, n, e)
+
+
+# ------------------------------------------------------------------------------------------------------------------ bench.py
+def test_bench_plain_run_times_the_steps_asked_for_and_dumps_the_last_steps_outputs(tmp_path):
+    """`python bench.py --steps K --dump-outputs DIR` without --full: one JSON line with the headline only (no leg that --full adds), `steps`
+    = K and `value` = frames / `ms_per_step`; DIR holds the last timed step's loss terms (the ones the line's final losses sum), the
+    attention and the fixed parameter samples, float32, 64 MB at most."""
+    import json
+    import os
+    import subprocess
+    import sys
+
+    import numpy as np
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "4",
+                        "--dump-outputs", str(tmp_path)], env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1, r.stdout
+    rec = json.loads(lines[0])
+    assert rec["steps"] == 3 and rec["warmup"] == 1 and rec["ms_per_step"] > 0
+    assert abs(rec["value"] - 4 * 325 / (rec["ms_per_step"] * 1e-3)) < 1e-3 * rec["value"]
+    for leg in ("roofline", "cpu_baseline", "stock_gpu_baseline"):
+        assert leg not in rec
+    assert not any(k.startswith(("text2mel_ms", "adversarial_", "fp32_exact_", "eager_", "ge2e_")) for k in rec["config"]), rec["config"]
+    files = sorted(os.listdir(tmp_path))
+    assert files == ["ssrn_losses.npy", "ssrn_params_sample.npy", "text2mel_attention.npy", "text2mel_losses.npy", "text2mel_params_sample.npy"]
+    assert sum(os.path.getsize(os.path.join(tmp_path, f)) for f in files) <= 64 << 20
+    got = {f[:-4]: np.load(os.path.join(tmp_path, f)) for f in files}
+    assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in got.values())
+    assert got["text2mel_attention"].shape == (4, 186, 325)
+    assert got["text2mel_losses"].shape == (3,) and got["ssrn_losses"].shape == (2,)
+    for kind in ("text2mel", "ssrn"):
+        assert abs(float(got[kind + "_losses"].sum()) - rec["config"]["final_loss_" + kind]) < 1e-4
+        assert got[kind + "_params_sample"].shape == (1 << 22,)

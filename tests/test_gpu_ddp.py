@@ -471,7 +471,7 @@ _REHEARSAL_RANKS = 4      # + this pytest process = 5 processes on the card; the
 
 
 def _rehearsal_args(n):
-    return ["--gpus", str(n), "--steps", "2", "--warmup", "1", "--batch", "4", "--check-replicas",
+    return ["--gpus", str(n), "--steps", "2", "--warmup", "1", "--batch", "4", "--check-replicas", "--full",
             "--no-cpu-baseline", "--no-ge2e", "--no-fp32", "--no-roofline"]
 
 
