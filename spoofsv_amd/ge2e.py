@@ -12,6 +12,7 @@ are constructor arguments whose defaults are that file's values (nmels 40, hidde
 proj 256; GE2E/config/config.yaml:16,21-23).
 """
 import ctypes
+import weakref
 
 import torch
 import torch.nn as nn
@@ -27,16 +28,19 @@ def _ptr_array(tensors):
     return arr
 
 
-_FWD_CACHE = {}       # the last inference call's workspace and what it was prepared for (see _EmbedderFn.forward)
+# SpeechEmbedder -> its last inference call's workspace and what it was prepared for (see _EmbedderFn.forward).  Keyed by
+# the module itself, weakly: an entry can only serve the module that wrote it and is freed with it.
+_FWD_CACHE = weakref.WeakKeyDictionary()
 
 
 class _EmbedderFn(torch.autograd.Function):
     """SpeechEmbedder.forward (speech_embedder_net.py:27-33) with its backward: LSTM stack -> last frame -> Linear -> x/|x|.
-    Inputs: train flag (keep every frame for the backward), x, projection weight, projection bias, then per layer
-    w_ih, w_hh, b_ih, b_hh."""
+    Inputs: ``cache`` (None: training, every frame is kept for the backward; otherwise the calling module's dict that keeps
+    the inference workspace), x, projection weight, projection bias, then per layer w_ih, w_hh, b_ih, b_hh."""
 
     @staticmethod
-    def forward(ctx, train, x, pw, pb, *lstm):
+    def forward(ctx, cache, x, pw, pb, *lstm):
+        train = cache is None
         layers = len(lstm) // 4
         Bn, T, F = x.shape
         H, P = lstm[1].shape[1], pw.shape[0]
@@ -52,13 +56,14 @@ class _EmbedderFn(torch.autograd.Function):
             _lib.call("ssv_lstm_train_fwd", _p(x), *args, _p(h_last), _p(saved), Bn, T, F, H, layers, _p(ws), nb, _stream())
         else:
             # d-vector extraction runs batch after batch on fixed weights: the workspace (with the split weight planes and their scale) is kept
-            # between calls and re-used as long as shape, arithmetic mode, stream and every weight's (address, version) are the same
+            # in the module's cache between calls and re-used as long as shape, arithmetic mode, stream and every weight's (address, version)
+            # are the same
             nb = _lib.query("ssv_lstm_fwd_workspace", Bn, T, F, H, layers)
             key = (Bn, T, F, H, layers, _lib.precision(), x.device, _stream().value, tuple((t.data_ptr(), t._version) for t in lstm))
-            hit = _FWD_CACHE.get("key") == key
-            ws = _FWD_CACHE["ws"] if hit else _ws(nb, x.device)
+            hit = cache.get("key") == key
+            ws = cache["ws"] if hit else _ws(nb, x.device)
             _lib.call("ssv_lstm_fwd_cached", _p(x), *args, _p(h_last), Bn, T, F, H, layers, _p(ws), nb, 1 if hit else 0, _stream())
-            _FWD_CACHE["key"], _FWD_CACHE["ws"] = key, ws
+            cache["key"], cache["ws"] = key, ws
         e = torch.empty((Bn, P), dtype=torch.float32, device=x.device)
         norms = torch.empty((Bn,), dtype=torch.float32, device=x.device) if train else None
         nb2 = _lib.query("ssv_proj_l2norm_fwd_workspace", Bn, P)
@@ -122,9 +127,15 @@ class SpeechEmbedder(nn.Module):
             params += [getattr(lstm, "%s_l%d" % (kind, l)) for kind in ("weight_ih", "weight_hh", "bias_ih", "bias_hh")]
         if self.training and torch.is_grad_enabled():
             # keeps every frame for backpropagation through time (ssv_lstm_saved_bytes: 5.8 GB at 880 x 120 frames)
-            return _EmbedderFn.apply(True, x, self.projection.weight, self.projection.bias, *params)
-        with torch.no_grad():       # d-vector extraction (GE2E/dvector_create.py:100): nothing is kept
-            return _EmbedderFn.apply(False, x, self.projection.weight, self.projection.bias, *params)
+            return _EmbedderFn.apply(None, x, self.projection.weight, self.projection.bias, *params)
+        with torch.no_grad():       # d-vector extraction (GE2E/dvector_create.py:100): nothing is kept but the workspace
+            return _EmbedderFn.apply(_FWD_CACHE.setdefault(self, {}), x, self.projection.weight, self.projection.bias, *params)
+
+    def invalidate(self):
+        """Drop the kept inference workspace (the split LSTM weight planes); the next call splits the weights again.  Calls
+        notice in-place torch updates of the weights (version) and rebinds (address) by themselves; call this after writing
+        weights through ``.data`` (``p.data.copy_(...)``), which leaves both unchanged."""
+        _FWD_CACHE.pop(self, None)
 
 
 class _GE2ELossFn(torch.autograd.Function):

@@ -1107,7 +1107,8 @@ class SpecLossFn(torch.autograd.Function):
 
     ``seed``: the (2,) gradient vector the caller promises to seed this output's backward with (a training step knows it before the
     forward runs: a constant).  Forward and backward then share ONE pass over (y, gt) (``ssv_spec_losses_fwd_bwd``) and the backward
-    hands out the stored dy -- provided it is really called with that tensor, unchanged; anything else takes the separate backward kernel."""
+    hands out the stored dy -- provided it is called with that very tensor (``is``), its version unchanged; anything else takes the
+    separate backward kernel and drops the stored dy."""
 
     @staticmethod
     def forward(ctx, y, gt, seed=None):
@@ -1124,8 +1125,7 @@ class SpecLossFn(torch.autograd.Function):
                 raise RuntimeError("spec loss: the promised gradient seed must be a contiguous float32 2-vector on the prediction's device")
             dy = torch.empty_like(y)
             _lib.call("ssv_spec_losses_fwd_bwd", _p(y), _p(gt), n, _p(seed), _p(out), _p(dy), _p(ws), nb, _stream())
-            ctx.fused = (dy, seed.data_ptr(), seed._version)
-            ctx.seed_ref = seed
+            ctx.fused = (dy, seed, seed._version)
         else:
             _lib.call("ssv_spec_losses_fwd", _p(y), _p(gt), n, _p(out), _p(ws), nb, _stream())
         ctx.save_for_backward(y, gt)
@@ -1135,8 +1135,9 @@ class SpecLossFn(torch.autograd.Function):
     def backward(ctx, gout):
         y, gt = ctx.saved_tensors
         f = ctx.fused
-        if f is not None and gout.data_ptr() == f[1] and ctx.seed_ref._version == f[2] and gout.is_contiguous():
+        if f is not None and gout is f[1] and gout._version == f[2]:
             return f[0], None, None
+        ctx.fused = None
         gout = _c(gout)
         dy = torch.empty_like(y)
         _lib.call("ssv_spec_losses_bwd", _p(y), _p(gt), y.numel(), _p(gout), _p(dy), _stream())
@@ -1212,6 +1213,7 @@ def attention_train(kv, q):
 
 
 def deconv1d_k2s2(x, w, bias):
+    resident.mark_transposed(w)          # the weight of a transposed convolution: its planes are kept for the 1x1 view
     if not (_f16() and _bf3_shape(x)):
         return DeconvK2S2Fn.apply(x, w, bias)
     ya = torch.empty((x.shape[0], 64), dtype=_F32, device=x.device)

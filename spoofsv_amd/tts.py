@@ -18,7 +18,7 @@ containers only (they give the reference's initialisation order and key names); 
 import torch
 import torch.nn as nn
 
-from . import ops
+from . import ops, resident
 
 
 class textEmbedding(nn.Module):
@@ -235,6 +235,7 @@ class upsampling(nn.Module):
     def __init__(self, ssrn_dim):
         super().__init__()
         self.deconv = nn.ConvTranspose1d(in_channels=ssrn_dim, out_channels=ssrn_dim, kernel_size=2, stride=2)
+        resident.mark_transposed(self.deconv.weight)
         self.hc1 = highwayConv(dimension=ssrn_dim, kernel_size=3, dilation=1)
         self.hc2 = highwayConv(dimension=ssrn_dim, kernel_size=3, dilation=3)
 

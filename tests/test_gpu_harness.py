@@ -391,6 +391,116 @@ def test_resident_weights_match_per_call_split_and_follow_weight_updates():
 
 
 @pytest.mark.gpu
+def test_resident_planes_do_not_pass_to_a_new_weight_at_an_old_address():
+    """Planes belong to the weight they were split from: a weight allocated after that one and its plane set are gone -- same shape, version 0,
+    in all likelihood the same address -- finds none."""
+    from spoofsv_amd import resident
+    w1 = torch.randn(128, 64, 3, device="cuda")
+    rw = resident.ResidentWeights([w1])
+    rw.refresh(torch.cuda.current_stream().cuda_stream)
+    assert resident.lookup(w1) is not None
+    del w1, rw
+    w2 = torch.randn(128, 64, 3, device="cuda")
+    assert resident.lookup(w2) is None
+
+
+@pytest.mark.gpu
+def test_a_plain_k2_conv_weight_is_not_packed_as_a_transposed_one():
+    """Only weights registered with ``resident.mark_transposed`` are packed as a ConvTranspose1d(k = 2, s = 2) weight: the (Cout, Cin, 2) weight
+    of an ordinary Conv1d(kernel_size=2) handed to FusedAdam gets no planes, under its own shape or the 1x1 view, and its layer computes as before."""
+    from spoofsv_amd import resident, train
+    torch.manual_seed(9)
+    conv = torch.nn.Conv1d(64, 96, kernel_size=2).to("cuda")
+    w = conv.weight
+    x = torch.randn(4, 64, 50, device="cuda")
+    dy = torch.randn(4, 96, 49, device="cuda")
+
+    def run():
+        xg = x.clone().requires_grad_(True)
+        conv.zero_grad(set_to_none=True)
+        y = torch.einsum("oik,bitk->bot", w, xg.unfold(2, 2, 1)) + conv.bias[:, None]      # the layer, on torch's GEMM
+        y.backward(dy)
+        return [y.detach().clone(), xg.grad.clone(), w.grad.clone(), conv.bias.grad.clone()]
+
+    base = run()
+    opt = train.FusedAdam(conv.parameters(), 1e-3)
+    opt.refresh_resident_weights()
+    assert not resident.eligible(w)
+    assert resident.lookup(w) is None and resident.lookup(w.view(96, 128, 1)) is None
+    for a, b in zip(base, run()):
+        assert torch.equal(a, b)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("mode", ["f16x2", "bf16x3"])
+def test_ssrn_upsampling_weights_are_resident(mode):
+    """``tts.upsampling`` registers its deconvolution weight as transposed, so an optimizer keeps its planes under the 1x1 view the
+    deconvolution looks them up with."""
+    import spoofsv_amd
+    from spoofsv_amd import resident, train
+    from spoofsv_amd.tts import SSRN
+    prev = spoofsv_amd.set_precision(mode)
+    try:
+        m = SSRN(80, 65, 32).to("cuda")
+        opt = train.FusedAdam(m.parameters(), 1e-3)
+        opt.refresh_resident_weights()
+        for ups in (m.ups1, m.ups2):
+            w = ups.deconv.weight
+            assert resident.lookup(w.view(w.shape[0], 2 * w.shape[1], 1)) is not None
+    finally:
+        spoofsv_amd.set_precision(prev)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("mode", ["f16x2", "bf16x3"])
+@pytest.mark.parametrize("kind", ["text2mel", "ssrn"])
+def test_bench_step_finds_every_resident_plane_and_fuses_the_spec_loss(kind, mode, monkeypatch):
+    """One eager step of the benchmark's training step (bench.py Trainer: its models, batch, optimizer and deferred weight gradients) after
+    ``refresh_resident_weights()``: every plane lookup of a conv weight the optimizer owns finds planes, and the spectrogram loss takes the fused
+    forward + backward pass (the backward is seeded with the vector promised to the forward)."""
+    import spoofsv_amd
+    from spoofsv_amd import _lib, resident, train
+    from spoofsv_amd.tts import SSRN, melSyn
+    prev = spoofsv_amd.set_precision(mode)
+    try:
+        torch.manual_seed(1234)
+        gaw = None
+        if kind == "text2mel":
+            model = melSyn(34, True, 200, textemb_dim=128, freq_bins=80, hidden_dim=256)
+            data = train.synthetic_text2mel_batch(32, 186, 325, seed=0, device="cuda")
+            gaw = train.guided_attention_mat(186, 325, device="cuda")
+        else:
+            model = SSRN(80, 513, 256)
+            data = train.synthetic_ssrn_batch(32, 325, seed=0, device="cuda")
+        model.apply(train.init_weights)
+        model.to("cuda").train()
+        opt = train.FusedAdam(model.parameters(), 2e-4, (0.5, 0.9), 1e-6, capturable=True)
+        opt.refresh_resident_weights()
+        owned = {id(p) for p in opt._resident.params}
+        found, missed, calls = [], [], []
+        lookup, call = resident.lookup, _lib.call
+
+        def counted_lookup(w):
+            r = lookup(w)
+            if id(w if w._base is None else w._base) in owned:
+                (found if r is not None else missed).append(tuple(w.shape))
+            return r
+
+        def counted_call(name, *args):
+            calls.append(name)
+            return call(name, *args)
+
+        monkeypatch.setattr(resident, "lookup", counted_lookup)
+        monkeypatch.setattr(_lib, "call", counted_call)
+        train.TrainStep(kind, model, opt, list(data), gaw, None, graph=False, defer_wgrad=True)()
+        torch.cuda.synchronize()
+        assert found and not missed, missed
+        assert "ssv_spec_losses_fwd_bwd" in calls and "ssv_spec_losses_bwd" not in calls
+    finally:
+        spoofsv_amd.set_precision(prev)
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("capturable", [False, True])
 def test_fused_adam_state_roundtrip_continues_bias_correction(capturable):
     """A FusedAdam restored from its state_dict takes exactly the step the original would have taken next

@@ -392,33 +392,69 @@ def test_ge2e_embedder_input_widths_and_magnitudes_vs_oracle(nmels, hidden, scal
     assert rel_err(eg, eo) < FWD_TOL and rel_l2(eg, eo) < FWD_TOL, (nmels, hidden, scale, rel_err(eg, eo), rel_l2(eg, eo))
 
 
-def test_ge2e_embedder_reuses_packed_weights_until_a_weight_changes():
+def test_ge2e_embedder_keeps_its_packed_weights_until_a_weight_changes():
     """d-vector extraction on fixed weights (GE2E/dvector_create.py:100): the second call of the same shape re-uses the split weight planes and
-    their scale in the kept workspace (ssv_lstm_fwd_cached) and returns the same bits; an in-place weight update is seen (version bump) and the
-    planes are rebuilt; a fresh module with the updated weights agrees."""
+    their scale in the workspace the module keeps (ssv_lstm_fwd_cached) and returns the same bits; an in-place weight update is seen (version
+    bump) and the planes are rebuilt; a fresh module with the updated weights agrees."""
     from spoofsv_amd import ge2e
     from spoofsv_amd.ge2e import SpeechEmbedder
     torch.manual_seed(6)
     m = SpeechEmbedder(nmels=40, hidden=64, num_layer=3, proj=32).to(DEV).eval()
     x = torch.randn(70, 9, 40, device=DEV)
-    ge2e._FWD_CACHE.clear()
+    cache = lambda: ge2e._FWD_CACHE[m]                                       # the workspace this module keeps
     e1 = m(x)
-    key1 = ge2e._FWD_CACHE["key"]
+    key1 = cache()["key"]
     e2 = m(x)
-    assert ge2e._FWD_CACHE["key"] == key1 and torch.equal(e1, e2)            # a hit: same workspace, same result
+    assert cache()["key"] == key1 and torch.equal(e1, e2)                    # a hit: same workspace, same result
     e3 = m(2 * x)                                                            # other data, same weights: still a hit, new input scale
-    assert ge2e._FWD_CACHE["key"] == key1 and not torch.equal(e3, e1)
+    assert cache()["key"] == key1 and not torch.equal(e3, e1)
     with torch.no_grad():
         m.LSTM_stack.weight_hh_l1.mul_(1.25)
     e4 = m(x)
-    assert ge2e._FWD_CACHE["key"] != key1 and not torch.equal(e4, e1)
+    assert cache()["key"] != key1 and not torch.equal(e4, e1)
     fresh = SpeechEmbedder(nmels=40, hidden=64, num_layer=3, proj=32)
     fresh.load_state_dict(m.state_dict())
-    ge2e._FWD_CACHE.clear()
     assert torch.equal(fresh.to(DEV).eval()(x), e4)
     with torch.no_grad():
         eo = GO.speech_embedder(x.cpu(), {k: v.cpu() for k, v in m.state_dict().items()})
     assert rel_err(e4, eo) < FWD_TOL, rel_err(e4, eo)
+
+
+def test_ge2e_embedder_never_uses_another_models_planes():
+    """The kept inference workspace belongs to the module that wrote it.  A model built where a deleted one lived (same shapes: the caching
+    allocator hands its weights the same addresses, and their version counters are equal) computes with its own weights; a write through
+    ``.data`` (no version bump) is picked up after ``invalidate()``; a deleted model's workspace is freed with it, without a garbage collection."""
+    from spoofsv_amd.ge2e import SpeechEmbedder
+    dims = dict(nmels=40, hidden=64, num_layer=3, proj=32)
+    x = torch.randn(70, 9, 40, generator=torch.Generator().manual_seed(7)).to(DEV)
+    oracle = lambda m: GO.speech_embedder(x.cpu(), {k: v.cpu() for k, v in m.state_dict().items()})
+    torch.cuda.synchronize()
+    before = torch.cuda.memory_allocated()
+    torch.manual_seed(1)
+    a = SpeechEmbedder(**dims).to(DEV).eval()
+    ea = a(x).cpu()
+    del a
+    torch.cuda.synchronize()
+    assert torch.cuda.memory_allocated() == before
+    torch.manual_seed(2)
+    b = SpeechEmbedder(**dims).to(DEV).eval()
+    eb = b(x)
+    assert not torch.equal(eb.cpu(), ea)
+    with torch.no_grad():
+        eo = oracle(b)
+    assert rel_err(eb, eo) < FWD_TOL, rel_err(eb, eo)
+    torch.manual_seed(3)
+    c = SpeechEmbedder(**dims)
+    for name, q in c.named_parameters():              # (no loop variable may hold one of b's tensors: b must be freed below)
+        b.get_parameter(name).data.copy_(q)
+    b.invalidate()
+    eb2 = b(x)
+    with torch.no_grad():
+        eo2 = oracle(b)
+    assert rel_err(eb2, eo2) < FWD_TOL, rel_err(eb2, eo2)
+    del b, eb, eb2
+    torch.cuda.synchronize()
+    assert torch.cuda.memory_allocated() == before
 
 
 def test_ge2e_loss_golden_and_known_answer():
