@@ -15,21 +15,22 @@ import torch
 import torch.nn.functional as F
 
 
-def lstm_stack(x, sd, num_layers, prefix="LSTM_stack"):
+def lstm_stack(x, sd, num_layers, prefix="LSTM_stack", dtype=torch.float32):
     """nn.LSTM(batch_first=True), speech_embedder_net.py:19,28.  x: (B, T, F) -> (B, T, H).
 
     Per layer l and step t:  gates = W_ih x_t + b_ih + W_hh h_{t-1} + b_hh, split as
     (i, f, g, o); c_t = sigmoid(f) c_{t-1} + sigmoid(i) tanh(g); h_t = sigmoid(o) tanh(c_t).
+    Computes in ``dtype`` on the device of ``x`` (the weights are converted; float64 serves the GPU tests as a reference).
     """
     B, T, _ = x.shape
-    inp = x.float()
+    inp = x.to(dtype)
     for l in range(num_layers):
-        w_ih = sd["%s.weight_ih_l%d" % (prefix, l)]
-        w_hh = sd["%s.weight_hh_l%d" % (prefix, l)]
-        b = sd["%s.bias_ih_l%d" % (prefix, l)] + sd["%s.bias_hh_l%d" % (prefix, l)]
+        w_ih = sd["%s.weight_ih_l%d" % (prefix, l)].to(device=x.device, dtype=dtype)
+        w_hh = sd["%s.weight_hh_l%d" % (prefix, l)].to(device=x.device, dtype=dtype)
+        b = (sd["%s.bias_ih_l%d" % (prefix, l)] + sd["%s.bias_hh_l%d" % (prefix, l)]).to(device=x.device, dtype=dtype)
         H = w_hh.shape[1]
-        h = torch.zeros(B, H)
-        c = torch.zeros(B, H)
+        h = inp.new_zeros(B, H)
+        c = inp.new_zeros(B, H)
         xp = F.linear(inp, w_ih)  # (B, T, 4H): input projection for all steps at once
         outs = []
         for t in range(T):
@@ -42,10 +43,10 @@ def lstm_stack(x, sd, num_layers, prefix="LSTM_stack"):
     return inp
 
 
-def speech_embedder(x, sd, num_layers=3):
-    """SpeechEmbedder.forward, speech_embedder_net.py:27-33: last frame -> Linear -> x/||x||."""
-    h = lstm_stack(x, sd, num_layers)[:, -1]
-    e = F.linear(h, sd["projection.weight"], sd["projection.bias"])
+def speech_embedder(x, sd, num_layers=3, dtype=torch.float32):
+    """SpeechEmbedder.forward, speech_embedder_net.py:27-33: last frame -> Linear -> x/||x||.  In ``dtype`` on x's device."""
+    h = lstm_stack(x, sd, num_layers, dtype=dtype)[:, -1]
+    e = F.linear(h, sd["projection.weight"].to(device=x.device, dtype=dtype), sd["projection.bias"].to(device=x.device, dtype=dtype))
     return e / torch.norm(e, dim=1).unsqueeze(1)
 
 
@@ -64,7 +65,7 @@ def ge2e_cossim(emb, centroids=None):
     loo = (emb.sum(dim=1, keepdim=True) - emb) / (M - 1)     # (N, M, D)
     cos = F.cosine_similarity(emb.unsqueeze(2), cent.view(1, 1, K, -1), dim=3)
     own = F.cosine_similarity(emb, loo, dim=2)               # (N, M)
-    idx = torch.arange(min(N, K))
+    idx = torch.arange(min(N, K), device=emb.device)
     cos = cos.clone()
     cos[idx, :, idx] = own[idx]
     return cos + 1e-6
@@ -79,7 +80,7 @@ def ge2e_loss(emb, w, b):
     """
     S = w * ge2e_cossim(emb) + b
     N = S.shape[0]
-    idx = torch.arange(N)
+    idx = torch.arange(N, device=S.device)
     pos = S[idx, :, idx]                                      # (N, M)
     per = -(pos - torch.log(torch.exp(S).sum(dim=2) + 1e-6))
     return per.sum(), per
@@ -87,20 +88,21 @@ def ge2e_loss(emb, w, b):
 
 def clip_grad_norm(grads, max_norm):
     """torch.nn.utils.clip_grad_norm_ (train_speech_embedder.py:84-85): scale every gradient by
-    min(1, max_norm / (||g||_2 + 1e-6)) with the norm taken over all of them.  Returns (scaled grads, norm)."""
-    total = torch.sqrt(sum((g.double() ** 2).sum() for g in grads)).float()
+    min(1, max_norm / (||g||_2 + 1e-6)) with the norm taken over all of them (in the gradients' dtype).  Returns (scaled grads, norm)."""
+    total = torch.sqrt(sum((g.double() ** 2).sum() for g in grads)).to(grads[0].dtype)
     coef = torch.clamp(max_norm / (total + 1e-6), max=1.0)
     return [g * coef for g in grads], total
 
 
-def ge2e_train_step(x, sd, w, b, N, M, num_layers=3, lr=0.01, clip_net=3.0, clip_loss=1.0):
+def ge2e_train_step(x, sd, w, b, N, M, num_layers=3, lr=0.01, clip_net=3.0, clip_loss=1.0, dtype=torch.float32, return_emb=False):
     """One iteration of GE2E/train_speech_embedder.py:70-86 (the batch permutation at :67-73 is undone at :78 and does not
     enter the arithmetic): loss, gradients by autograd over this restatement, clip_grad_norm_(3.0) on the embedder and
-    (1.0) on (w, b), plain SGD.  Returns (loss, grads dict, (dw, db), new sd, (new w, new b))."""
-    p = {k: v.detach().clone().requires_grad_(True) for k, v in sd.items()}
-    wv = torch.tensor(float(w), requires_grad=True)
-    bv = torch.tensor(float(b), requires_grad=True)
-    emb = speech_embedder(x, p, num_layers)
+    (1.0) on (w, b), plain SGD.  Parameters, loss and gradients are in ``dtype`` on x's device.
+    Returns (loss, grads dict, (dw, db), new sd, (new w, new b)), and the embeddings after them if ``return_emb``."""
+    p = {k: v.detach().to(device=x.device, dtype=dtype).clone().requires_grad_(True) for k, v in sd.items()}
+    wv = torch.tensor(float(w), dtype=dtype, device=x.device, requires_grad=True)
+    bv = torch.tensor(float(b), dtype=dtype, device=x.device, requires_grad=True)
+    emb = speech_embedder(x, p, num_layers, dtype=dtype)
     loss, _ = ge2e_loss(emb.reshape(N, M, -1), wv, bv)
     loss.backward()
     keys = list(p.keys())
@@ -108,7 +110,8 @@ def ge2e_train_step(x, sd, w, b, N, M, num_layers=3, lr=0.01, clip_net=3.0, clip
     gnet, _ = clip_grad_norm([grads[k] for k in keys], clip_net)
     gloss, _ = clip_grad_norm([wv.grad, bv.grad], clip_loss)
     new_sd = {k: (p[k].detach() - lr * g) for k, g in zip(keys, gnet)}
-    return loss.detach(), grads, (wv.grad.clone(), bv.grad.clone()), new_sd, (wv.detach() - lr * gloss[0], bv.detach() - lr * gloss[1])
+    out = (loss.detach(), grads, (wv.grad.clone(), bv.grad.clone()), new_sd, (wv.detach() - lr * gloss[0], bv.detach() - lr * gloss[1]))
+    return out + (emb.detach(),) if return_emb else out
 
 
 def eer_sweep(sim_matrix, size_1, es1, spoof=True):

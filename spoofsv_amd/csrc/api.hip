@@ -136,7 +136,7 @@ int ssv_launch_transpose_out(const float*, float*, int, int, hipStream_t);
 int ssv_launch_l2norm_rows(const float*, float*, float*, int, int, hipStream_t);
 int ssv_launch_l2norm_bwd(const float*, const float*, const float*, float*, int, int, hipStream_t);
 int ssv_launch_colsum(const float*, float*, int, int, hipStream_t);
-int ssv_launch_lstm_cell_bwd(const float*, const float*, const float*, long, int, const float*, float*, float*, float*, int, int, int, int, int, int, int, hipStream_t);
+int ssv_launch_lstm_cell_bwd(const float*, const float*, const float*, long, int, const float*, float*, float*, float*, float*, int, int, int, int, int, int, int, hipStream_t);
 
 static inline size_t align256(size_t n) { return (n + 255) & ~(size_t)255; }
 
@@ -1405,7 +1405,11 @@ extern "C" int ssv_lstm_train_fwd(const float* x, const float* const* w_ih, cons
                        (float*)(sb + sv.xt), (float*)(sb + sv.hs), (float*)(sb + sv.cs), (float*)(sb + sv.gates));
 }
 
-struct LstmBwdWs { size_t dgates, dxa, dxa_slab, dcarry, dhtop, rs, wta, wta_stride, slabs, total; };
+struct LstmBwdWs { size_t dgates, dxa, dxa_slab, dcarry, dhtop, rs, wta, wta_stride, cmax, aux, slabs, total; };
+// split-fp16 scales of the backward (floats at `aux`): [0, 64) partial maxima of the weights of the data-gradient products (one scale for all
+// layers, as in the forward), [64] its inverse scale, [128, 192) the input frames' list, [192] 1.0 -- the list of the recurrent activations
+// (|h| < 1) --, then 64 entries per layer: that layer's dgates over all frames (the weight gradients' list), reduced from cmax.
+#define LSTM_BWD_AUX_FLOATS(layers) (256 + 64 * (layers))
 static size_t lstm_dw_slab_bytes(int Bn, int T, int H, int Fin) {
   return align256((size_t)dw_splits(T, 4 * H, Fin, 1, Bn) * 4 * H * Fin * sizeof(float));        // "batch" = frames, reduction length = utterances
 }
@@ -1422,16 +1426,20 @@ static LstmBwdWs lstm_bwd_ws(int Bn, int T, int F, int H, int layers) {
   s.rs = s.dhtop + align256((size_t)H * Bn * sizeof(float));
   s.wta = s.rs + align256((size_t)layers * T * 4 * H * sizeof(float));      // the bias gradients' per-frame terms, [layer][frame][4H] (lstm_cell_bwd_kernel)
   s.wta_stride = 2 * split_bytes(2 * H, 4 * H, 1);                 // [W_ih | W_hh]^T of a layer (layer 0: the W_ih half stays zero)
-  s.slabs = s.wta + (size_t)layers * s.wta_stride;
+  s.cmax = s.wta + (size_t)layers * s.wta_stride;                  // max |dgates| per (layer, frame, hidden unit), left by lstm_cell_bwd_kernel
+  s.aux = s.cmax + align256((size_t)layers * T * H * sizeof(float));
+  s.slabs = s.aux + align256(LSTM_BWD_AUX_FLOATS(layers) * sizeof(float));
   // every (items, M, Nc) lstm_weight_grad is called with: W_ih over T frames (Fin = F or H), W_hh over T - 1
   s.total = s.slabs + zmax(zmax(lstm_dw_slab_bytes(Bn, T, H, H), lstm_dw_slab_bytes(Bn, T > 1 ? T - 1 : 1, H, H)), lstm_dw_slab_bytes(Bn, T, H, F));
   return s;
 }
 extern "C" size_t ssv_lstm_bwd_workspace(int Bn, int T, int F, int H, int layers) { return lstm_bwd_ws(Bn, T, F, H, layers).total; }
-// dW (M x Nc) = sum over `items` frames of A_item (M x Bn) X_item^T (Nc x Bn): the conv weight-gradient kernel with time = batch
+// dW (M x Nc) = sum over `items` frames of A_item (M x Bn) X_item^T (Nc x Bn): the conv weight-gradient kernel with time = batch.
+// al / xl (split-fp16): the operands' scale lists, one per operand over all frames; null in the other modes.
 static int lstm_weight_grad(const float* A, long sab, const float* X, long sxb, float* dw, int M, int Nc, int Bn, int items, void* slabs, hipStream_t st,
-                            bool f32 = false) {
+                            bool f32 = false, const AmaxList* al = nullptr, const AmaxList* xl = nullptr) {
   GemmNT g = nt_zero();
+  if (al && xl) { g.f16 = 1; g.a_amax = al->p; g.a_namax = al->n; g.x_amax = xl->p; g.x_namax = xl->n; }
   const int Z = dw_splits(items, M, Nc, 1, Bn);
   const long n = (long)M * Nc;
   g.A = A; g.sab = sab; g.sam = Bn; g.La = Bn;
@@ -1452,6 +1460,8 @@ extern "C" int ssv_lstm_bwd(const float* dh_last, const void* saved, const float
                             int Bn, int T, int F, int H, int layers, void* ws, size_t ws_bytes, ssv_stream_t stream) {
   SSV_CHECK(dh_last && saved && w_ih && w_hh && dw_ih && dw_hh && db_ih && db_hh && Bn > 0 && T > 0 && F > 0 && H > 0 && layers > 0, SSV_BAD_SHAPE, "lstm_bwd: bad argument");
   const bool f32 = !lstm_train_split_ok(Bn, H);                    // the exact-fp32 products (see lstm_train_fwd_f32)
+  // split-fp16 products in the default mode, as in the forward (lstm_fwd_wave; one weight scale for all layers: at most 32 of them), split-bf16 in its mode
+  const bool f16 = !f32 && use_f16() && 2 * layers <= 64;
   const LstmBwdWs s = lstm_bwd_ws(Bn, T, F, H, layers);
   SSV_CHECK(ws && ws_bytes >= s.total, SSV_BAD_SHAPE, "lstm_bwd: workspace too small (%zu < %zu)", ws_bytes, s.total);
   hipStream_t st = (hipStream_t)stream;
@@ -1467,6 +1477,8 @@ extern "C" int ssv_lstm_bwd(const float* dh_last, const void* saved, const float
   float* dcarry = (float*)(base + s.dcarry);
   float* dhtop = (float*)(base + s.dhtop);
   float* rs = (float*)(base + s.rs);
+  float* cmax = f16 ? (float*)(base + s.cmax) : nullptr;
+  float* aux = (float*)(base + s.aux);
   const long HN = (long)H * Bn;
   const long zstride = (long)(s.dxa_slab / sizeof(float));
   SSV_TRY(ssv_launch_transpose_out(dh_last, dhtop, Bn, H, st));               // (Bn, H) -> [H][Bn]
@@ -1481,7 +1493,7 @@ extern "C" int ssv_lstm_bwd(const float* dh_last, const void* saved, const float
   };
   for (int step = T + layers - 2; f32 && step >= 0; --step) {
     const int lo = step - T + 1 > 0 ? step - T + 1 : 0, hi = step < layers - 1 ? step : layers - 1;
-    SSV_TRY(ssv_launch_lstm_cell_bwd(gates, cs, dxa, zstride, 1, dhtop, dgates, dcarry, rs, H, Bn, T, layers, step, lo, hi - lo + 1, st));
+    SSV_TRY(ssv_launch_lstm_cell_bwd(gates, cs, dxa, zstride, 1, dhtop, dgates, dcarry, rs, nullptr, H, Bn, T, layers, step, lo, hi - lo + 1, st));
     float* outp = dxa + (long)(step & 1) * layers * 2 * HN;                   // this step's parity
     if (lo == 0 && step >= 1) SSV_TRY(wt_gemm_f32(w_hh[0], dgates + (long)step * 4 * HN, outp + HN));
     for (int l = lo > 1 ? lo : 1; l <= hi; ++l) {                            // [dh^{l-1}_t ; dh^l_{t-1}] = [W_ih | W_hh]^T dgates^l_t
@@ -1492,14 +1504,26 @@ extern "C" int ssv_lstm_bwd(const float* dh_last, const void* saved, const float
   }
   // transposed weights for the data-gradient products: rows = inputs of the layer, reduction over the 4H gate rows
   const size_t rows_h = (size_t)(H / 16) * (4 * H / 32) * 512;               // elements of the first H rows of a [2H x 4H] plane
+  if (f16) {                                                                 // the weights' partial maxima: W_ih[l >= 1] and W_hh[l] (layer 0's W_ih half is zero)
+    const int npb = 64 / (2 * layers);
+    SSV_HIP(hipMemsetAsync(aux, 0, 64 * sizeof(float), st));
+    for (int l = 0; l < layers; ++l) {
+      if (l > 0) SSV_TRY(ssv_launch_absmax(w_ih[l], 0, 1, (long)4 * H * H, aux + (2 * l) * npb, npb, st));
+      SSV_TRY(ssv_launch_absmax(w_hh[l], 0, 1, (long)4 * H * H, aux + (2 * l + 1) * npb, npb, st));
+    }
+  }
+  auto pack_t = [&](const float* w, unsigned short* hi, unsigned short* lo) -> int {           // (m=q, k=r) = W[r][q]
+    if (f16) return ssv_launch_pack_split_f16_list(w, hi, lo, H, 4 * H, 4 * H, 1, 1, H, 1, 0, aux, 64, aux + 64, st);
+    return ssv_launch_pack_split(w, hi, lo, H, 4 * H, 4 * H, 1, 1, H, 1, 0, st);
+  };
   for (int l = 0; !f32 && l < layers; ++l) {
     unsigned short* hi = (unsigned short*)(base + s.wta + (size_t)l * s.wta_stride);
     unsigned short* lo = (unsigned short*)((char*)hi + split_bytes(2 * H, 4 * H, 1));
     if (l == 0) {                                                            // no data gradient of the utterance itself: zero rows (mostly skipped, see skip_rows)
       SSV_HIP(hipMemsetAsync(hi, 0, rows_h * sizeof(unsigned short), st));
       SSV_HIP(hipMemsetAsync(lo, 0, rows_h * sizeof(unsigned short), st));
-    } else SSV_TRY(ssv_launch_pack_split(w_ih[l], hi, lo, H, 4 * H, 4 * H, 1, 1, H, 1, 0, st));               // (m=q, k=r) = W_ih[r][q]
-    SSV_TRY(ssv_launch_pack_split(w_hh[l], hi + rows_h, lo + rows_h, H, 4 * H, 4 * H, 1, 1, H, 1, 0, st));
+    } else SSV_TRY(pack_t(w_ih[l], hi, lo));
+    SSV_TRY(pack_t(w_hh[l], hi + rows_h, lo + rows_h));
   }
   // ONE product launch per reverse wavefront step: every active layer (layer 0 included) x two K ranges of 2H gate rows, on the forward wavefront's
   // 128 x 128 tile -- 3 layers x 12 x 7 x 2 = 504 tiles less layer 0's 84 skipped ones for config 5 (before round 6's end: a 768-row and a 1536-row product
@@ -1507,25 +1531,36 @@ extern "C" int ssv_lstm_bwd(const float* dh_last, const void* saved, const float
   GemmNNB g = nnb_zero();
   g.Kpad = 4 * H; g.Kc = 2 * H; g.ksplit = 2; g.sxc = Bn; g.Lx = Bn; g.scm = Bn; g.N = Bn; g.M = 2 * H;
   g.sab = (long)(s.wta_stride / sizeof(unsigned short)); g.sxb = (long)(T - 1) * 4 * HN; g.scb = 2 * HN; g.scz = zstride;
+  // split-fp16: item b (layer lo + b at frame step - lo - b) takes the H maxima its cells just left, at the same (T - 1)-frame stride as its dgates
+  if (f16) { g.f16 = 1; g.a_inv = aux + 64; g.x_namax = H; g.x_amax_bs = (long)(T - 1) * H; }
   for (int step = T + layers - 2; !f32 && step >= 0; --step) {
     const int lo = step - T + 1 > 0 ? step - T + 1 : 0, hi = step < layers - 1 ? step : layers - 1;
-    SSV_TRY(ssv_launch_lstm_cell_bwd(gates, cs, dxa, zstride, 2, dhtop, dgates, dcarry, rs, H, Bn, T, layers, step, lo, hi - lo + 1, st));
+    SSV_TRY(ssv_launch_lstm_cell_bwd(gates, cs, dxa, zstride, 2, dhtop, dgates, dcarry, rs, cmax, H, Bn, T, layers, step, lo, hi - lo + 1, st));
     if (step == 0) break;                                                    // frame 0 of layer 0: its product would be the gradient of the initial state
     g.Ahi = (unsigned short*)(base + s.wta + (size_t)lo * s.wta_stride);
     g.Alo = (unsigned short*)((char*)g.Ahi + split_bytes(2 * H, 4 * H, 1));
     g.X = dgates + ((long)lo * T + (step - lo)) * 4 * HN;
+    if (f16) g.x_amax = cmax + ((long)lo * T + (step - lo)) * H;
     g.C = dxa + ((long)(step & 1) * layers + lo) * 2 * HN;
     g.B = hi - lo + 1;
     g.skip_rows = lo == 0 ? H : 0;
     SSV_TRY(ssv_launch_gemm_nn_bf3(g, st));
   }
   // parameter gradients: one reduction over all frames per matrix
+  // split-fp16 scale lists: the input frames' (one scan of xt), the recurrent activations' constant 1.0 (|h| < 1), a layer's dgates from its cells' maxima
+  AmaxList xl = {nullptr, 0}, hl = {aux + 192, 1};
+  if (f16) {
+    SSV_TRY(ssv_launch_fill(aux + 192, 1.f, 1, st));
+    SSV_TRY(amax_of(xt, 0, 1, (long)T * F * Bn, nullptr, 0, aux + 128, &xl, st));
+  }
   for (int l = 0; l < layers; ++l) {
     const float* dg = dgates + (long)l * T * 4 * HN;
     const int Fin = l == 0 ? F : H;
     const float* in = l == 0 ? xt : hs + (long)(l - 1) * T * HN;
-    SSV_TRY(lstm_weight_grad(dg, 4 * HN, in, (long)Fin * Bn, dw_ih[l], 4 * H, Fin, Bn, T, base + s.slabs, st, f32));
-    if (T > 1) SSV_TRY(lstm_weight_grad(dg + 4 * HN, 4 * HN, hs + (long)l * T * HN, HN, dw_hh[l], 4 * H, H, Bn, T - 1, base + s.slabs, st, f32));
+    AmaxList al = {nullptr, 0};
+    if (f16) SSV_TRY(amax_of(cmax + (long)l * T * H, 0, 1, (long)T * H, nullptr, 0, aux + 256 + 64 * l, &al, st));
+    SSV_TRY(lstm_weight_grad(dg, 4 * HN, in, (long)Fin * Bn, dw_ih[l], 4 * H, Fin, Bn, T, base + s.slabs, st, f32, f16 ? &al : nullptr, l == 0 ? &xl : &hl));
+    if (T > 1) SSV_TRY(lstm_weight_grad(dg + 4 * HN, 4 * HN, hs + (long)l * T * HN, HN, dw_hh[l], 4 * H, H, Bn, T - 1, base + s.slabs, st, f32, f16 ? &al : nullptr, &hl));
     else SSV_TRY(ssv_launch_fill(dw_hh[l], 0.f, (long)4 * H * H, st));
     SSV_TRY(ssv_launch_reduce_slabs(rs + (long)l * T * 4 * H, db_ih[l], 4 * H, T, 4 * H, st));      // sum over frames of sum_b dgates[l][t][r][b] (the cell kernel's row sums)
     SSV_HIP(hipMemcpyAsync(db_hh[l], db_ih[l], (size_t)4 * H * sizeof(float), hipMemcpyDeviceToDevice, st));

@@ -354,13 +354,16 @@ extern "C" int ssv_ge2e_loss_bwd(const float* emb, const float* w, const float* 
 // One workgroup per hidden unit u (a row of Bn utterances) and layer: besides the cells it leaves the row sums of the four gate gradients --
 // the bias gradient's terms of this frame, dbp[l][t][gate * H + u] -- in a fixed order (per thread over its columns, the 64 lanes of a wave by
 // ssv_wave_sum, the four waves in turn): the separate pass over all of dgates (ssv_rowsum: 3 x 0.22 ms for config 5) is gone.
+// amax != null (split-fp16 products): the workgroup also leaves max |dgates| over its four rows at amax[(l T + t) H + u] -- the scale list of the
+// data-gradient product that reads these dgates next and, reduced over the frames, of the layer's weight gradients: no pass over dgates for them.
 // V = 4: Bn % 4 == 0, a thread takes four neighbouring columns as 16-byte vectors (every row then starts 16-byte aligned); V = 1: any Bn.
 template <int V>
 __global__ __launch_bounds__(256) void lstm_cell_bwd_kernel(const float* __restrict__ gates, const float* __restrict__ cs, const float* __restrict__ dxa,
                                                             const long zstride, const int nz, const float* __restrict__ dh_top, float* __restrict__ dgates,
-                                                            float* __restrict__ dcarry, float* __restrict__ dbp, int H, int Bn, int T, int layers, int s, int lo) {
+                                                            float* __restrict__ dcarry, float* __restrict__ dbp, float* __restrict__ amax, int H, int Bn, int T,
+                                                            int layers, int s, int lo) {
   typedef float vec __attribute__((ext_vector_type(V)));
-  __shared__ float red[4][4];
+  __shared__ float red[4][5];
   const int u = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const long HN = (long)H * Bn;
   const int l = lo + blockIdx.y, t = s - l;
@@ -372,6 +375,7 @@ __global__ __launch_bounds__(256) void lstm_cell_bwd_kernel(const float* __restr
   vec sum[4];
 #pragma unroll
   for (int g = 0; g < 4; ++g) sum[g] = (vec)0.f;
+  float mx = 0.f;
   // every load of a pass in front of its first store (a load issued behind a store waits for it: one vmcnt)
   for (int b = tid * V; b < Bn; b += 256 * V) {
     const long i = (long)u * Bn + b;
@@ -396,6 +400,8 @@ __global__ __launch_bounds__(256) void lstm_cell_bwd_kernel(const float* __restr
     st(dgates + gt + 2 * HN + i, dg);
     st(dgates + gt + 3 * HN + i, d_o);
     sum[0] += di; sum[1] += df; sum[2] += dg; sum[3] += d_o;
+#pragma unroll
+    for (int k = 0; k < V; ++k) mx = fmaxf(mx, fmaxf(fmaxf(fabsf(di[k]), fabsf(df[k])), fmaxf(fabsf(dg[k]), fabsf(d_o[k]))));
   }
 #pragma unroll
   for (int g = 0; g < 4; ++g) {
@@ -404,15 +410,21 @@ __global__ __launch_bounds__(256) void lstm_cell_bwd_kernel(const float* __restr
     v = ssv_wave_sum(v);
     if (lane == 0) red[wave][g] = v;
   }
+  if (amax) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
+    if (lane == 0) red[wave][4] = mx;
+  }
   __syncthreads();
   if (tid < 4) dbp[((long)l * T + t) * 4 * H + (long)tid * H + u] = ((red[0][tid] + red[1][tid]) + red[2][tid]) + red[3][tid];
+  if (amax && tid == 4) amax[((long)l * T + t) * H + u] = fmaxf(fmaxf(red[0][4], red[1][4]), fmaxf(red[2][4], red[3][4]));
 }
 int ssv_launch_lstm_cell_bwd(const float* gates, const float* cs, const float* dxa, long zstride, int nz, const float* dh_top, float* dgates, float* dcarry,
-                             float* dbp, int H, int Bn, int T, int layers, int s, int lo, int nl, hipStream_t st) {
+                             float* dbp, float* amax, int H, int Bn, int T, int layers, int s, int lo, int nl, hipStream_t st) {
   // (the vector form also wants 16-byte aligned bases: the workspace sections are 256-byte aligned, the saved tensors come from the caller)
   const bool v4 = Bn % 4 == 0 && zstride % 4 == 0 && (((uintptr_t)gates | (uintptr_t)cs | (uintptr_t)dxa | (uintptr_t)dh_top | (uintptr_t)dgates | (uintptr_t)dcarry) & 15) == 0;
-  if (v4) hipLaunchKernelGGL(lstm_cell_bwd_kernel<4>, dim3(H, nl), dim3(256), 0, st, gates, cs, dxa, zstride, nz, dh_top, dgates, dcarry, dbp, H, Bn, T, layers, s, lo);
-  else hipLaunchKernelGGL(lstm_cell_bwd_kernel<1>, dim3(H, nl), dim3(256), 0, st, gates, cs, dxa, zstride, nz, dh_top, dgates, dcarry, dbp, H, Bn, T, layers, s, lo);
+  if (v4) hipLaunchKernelGGL(lstm_cell_bwd_kernel<4>, dim3(H, nl), dim3(256), 0, st, gates, cs, dxa, zstride, nz, dh_top, dgates, dcarry, dbp, amax, H, Bn, T, layers, s, lo);
+  else hipLaunchKernelGGL(lstm_cell_bwd_kernel<1>, dim3(H, nl), dim3(256), 0, st, gates, cs, dxa, zstride, nz, dh_top, dgates, dcarry, dbp, amax, H, Bn, T, layers, s, lo);
   return ssv_check_launch("lstm_cell_bwd");
 }
 

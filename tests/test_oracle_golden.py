@@ -3,7 +3,7 @@
 import numpy as np
 import torch
 
-from _golden import load, sub, t, rel_err
+from _golden import load, sub, t, rel_err, rel_l2
 from oracle import critic_oracle as CO
 from oracle import ge2e_oracle as GO
 from oracle import tts_oracle as TO
@@ -225,3 +225,28 @@ def test_ge2e_training_iteration():
     # verification-style similarity (enrollment centroids of another set), train_speech_embedder.py:156-159
     assert rel_err(GO.ge2e_cossim(t(g["ev_ver"]), t(g["ev_cent"])), t(g["ev_sim"])) < 1e-5
     assert rel_err(t(g["ev_enr"]).mean(dim=1), t(g["ev_cent"])) < 1e-6
+
+
+def test_ge2e_oracle_runs_in_float64():
+    """The GPU tests hold the embedder's training iteration to a float64 run of this oracle: with dtype=float64 every output is float64
+    and agrees with the float32 run (whose pins are the tests above) to float32 rounding -- 1e-7 on the loss and the embeddings; the gradients
+    are sums with cancellation (the projection bias: a column sum of GE2E's per-embedding terms), measured 1.4e-6 .. 6.2e-5 in rel_l2."""
+    g = load("ge2e_train.npz")
+    N, M, T, H, P = [int(v) for v in g["dims"]]
+    sd = {k[3:]: t(v) for k, v in g.items() if k.startswith("p0/")}
+    x, w0, b0 = t(g["x"]), float(g["w0"]), float(g["b0"])
+    r32 = GO.ge2e_train_step(x, sd, w0, b0, N, M, return_emb=True)
+    r64 = GO.ge2e_train_step(x, sd, w0, b0, N, M, dtype=torch.float64, return_emb=True)
+    loss32, grads32, dwb32, sd32, wb32, e32 = r32
+    loss64, grads64, dwb64, sd64, wb64, e64 = r64
+    assert loss64.dtype == torch.float64 and e64.dtype == torch.float64 and all(v.dtype == torch.float64 for v in grads64.values())
+    assert abs(float(loss32) - float(loss64)) < 1e-6 * abs(float(loss64))
+    assert rel_err(e32, e64) < 1e-6
+    for k in grads64:
+        assert rel_l2(grads32[k], grads64[k]) < 2e-4, (k, rel_l2(grads32[k], grads64[k]))
+        assert rel_l2(sd32[k], sd64[k]) < 1e-6, k
+    for a, b in zip(dwb32 + wb32, dwb64 + wb64):
+        assert abs(float(a) - float(b)) < 1e-6
+    # the float32 default is what it was: bit for bit the explicit float32 call, on float32 tensors
+    e = GO.speech_embedder(x, sd)
+    assert e.dtype == torch.float32 and torch.equal(e, GO.speech_embedder(x, sd, dtype=torch.float32))
