@@ -293,6 +293,31 @@ int ssv_guided_att_loss_fwd(const float* a, const float* gaw, int gaw_T, float* 
 int ssv_guided_att_loss_bwd(const float* gaw, int gaw_T, const float* gscale, float* da, int B, int N, int T,
                             ssv_stream_t stream);
 
+/* ---- length-masked training steps (additions; ABI version unchanged) ---------------------------------------------------------
+ * One hipGraph captured at a bucket shape (N, T) serves every batch whose own maxima N_b <= N, T_b <= T (the reference's collates pad to
+ * the batch's longest item, data/dataset.py:187-258).  `live` is a DEVICE int pointer to the live length (N_b or T_b), read by the
+ * kernels at run time; `mult` scales it inside SSRN's upsampled stages (2 T_b, 4 T_b).  Live lengths are clamped to the tensor's extent.
+ * ssv_mask_cols: x(b, c, t) = 0 for t >= mult * live[0] (x: (B, C, L), rows of L, batch stride x_bs); writes only the tail columns.
+ * A layer's output masked this way, and its incoming gradient masked the same way before its backward runs, make every convolution see
+ * the zero padding of the unpadded shape, and parameter gradients receive nothing from the padded columns. */
+int ssv_mask_cols(float* x, long x_bs, int B, int C, int L, const int* live, int mult, ssv_stream_t stream);
+/* models/TTSModel.py:266-270 on a padded batch: live[0] = N_b, live[1] = T_b.  Keys n >= N_b are left out of the column softmax (A = 0
+ * there); columns t >= T_b of A and of R are 0.  Same outputs as ssv_attention_train_fwd_rq otherwise; the backward is
+ * ssv_attention_train_bwd (A = 0 makes dS, dK, dV, dQ zero on the masked sets). */
+int ssv_attention_train_fwd_rq_len(const float* k, const float* v, long kv_bs, const float* q, long q_bs, float* a, float* rq, long rq_bs,
+                                   int B, int d, int N, int T, const int* live, ssv_stream_t stream);
+/* train/ordinary.py:230-231 / :249-250 over the live columns t < mult * live[0] of (B, C, L) tensors, divided by B * C * (mult * live[0]);
+ * dy (may be NULL; then gscale may be NULL too) receives the gradient for the DEVICE seed gscale (2 floats) inside the live columns and 0
+ * outside.  Workspace ssv_spec_losses_workspace(B * C * L). */
+int ssv_spec_losses_len(const float* y, const float* gt, int B, int C, int L, const int* live, int mult, const float* gscale,
+                        float* out, float* dy, void* ws, size_t ws_bytes, ssv_stream_t stream);
+/* train/ordinary.py:232-234 over the live block n < live[0], t < live[1]: sum(a * gaw) / (B * N_b * T_b); the backward writes 0 outside the
+ * block.  Workspace ssv_guided_att_loss_workspace(B, N, T). */
+int ssv_guided_att_loss_fwd_len(const float* a, const float* gaw, int gaw_T, float* out, int B, int N, int T, const int* live,
+                                void* ws, size_t ws_bytes, ssv_stream_t stream);
+int ssv_guided_att_loss_bwd_len(const float* gaw, int gaw_T, const float* gscale, float* da, int B, int N, int T, const int* live,
+                                ssv_stream_t stream);
+
 /* ---- Resident pre-split weights ------------------------------------------------------------------
  * The split-bf16 conv kernels read weights as bf16 hi/lo planes in MFMA fragment order.  Splitting a weight costs one
  * small launch per conv call (forward order for the forward, transposed order for the data gradient): ~100 launches

@@ -804,6 +804,24 @@ extern "C" int ssv_attention_train_fwd_rq(const float* k, const float* v, long k
   SSV_TRY(ssv_attention_train_fwd(k, v, kv_bs, q, q_bs, a, rq, rq_bs, B, d, N, T, stream));
   return ssv_copy_rows(q, q_bs, rq + (long)d * T, rq_bs, B, (long)d * T, stream);
 }
+// Length-masked form: scores on the general product, the masked column softmax (attn.hip), V A.  The fused one-launch kernel has no mask; the
+// backward is ssv_attention_train_bwd unchanged (A is exactly 0 on the masked sets, hence so are dS, dK, dV and dQ there).
+int ssv_launch_softmax_cols_len(float* s, int B, int N, int T, const int* live, hipStream_t st);
+extern "C" int ssv_attention_train_fwd_rq_len(const float* k, const float* v, long kv_bs, const float* q, long q_bs, float* a, float* rq, long rq_bs,
+                                              int B, int d, int N, int T, const int* live, ssv_stream_t stream) {
+  SSV_CHECK(k && v && q && a && rq && live && B > 0 && d > 0 && N > 0 && T > 0 && rq_bs >= (long)2 * d * T, SSV_BAD_SHAPE,
+            "attention_train_fwd_rq_len: bad argument");
+  hipStream_t st = (hipStream_t)stream;
+  GemmNN g = nn_zero();
+  g.A = k; g.sab = kv_bs; g.sam = 1; g.sac = N; g.saj = 0;
+  g.X = q; g.sxb = q_bs; g.sxc = T; g.Lx = T;
+  g.C = a; g.scb = (long)N * T; g.scm = T;
+  g.M = N; g.N = T; g.Kc = d; g.B = B; g.alpha = 1.f / sqrtf((float)d);
+  SSV_TRY(ssv_launch_gemm_nn(g, st));
+  SSV_TRY(ssv_launch_softmax_cols_len(a, B, N, T, live, st));
+  SSV_TRY(ssv_attention_apply(v, kv_bs, a, T, rq, rq_bs, B, d, N, T, stream));
+  return ssv_copy_rows(q, q_bs, rq + (long)d * T, rq_bs, B, (long)d * T, stream);
+}
 extern "C" size_t ssv_attention_train_bwd_workspace(int B, int d, int N, int T) { (void)d; return align256((size_t)B * N * T * sizeof(float)) + 2 * AMAX_FB_BYTES; }
 // Per-batch-item products reduced over time (attention dV, dK): the split-bf16 weight-gradient kernel with one slab per batch
 // item and no slab sum (21 -> ~100 TFLOP/s at d = 256, N = 186, T = 325; the fp32 kernel's 128 x 96 tiles leave the chip idle).

@@ -134,6 +134,31 @@ int ssv_launch_softmax_cols_bwd(const float* a, float* da, const float* da_ext, 
   return ssv_check_launch("softmax_cols_bwd");
 }
 
+// Column softmax of a length-masked step: live[0] = N_b text positions, live[1] = T_b frames (device ints, clamped to N, T).  Keys n >= N_b are
+// left out of the softmax and get A = 0; columns t >= T_b are all zero.  The backward needs no mask of its own: dS = A (dA - sum A dA) is 0
+// wherever A is.  One thread per (b, t) column as softmax_cols_kernel; same arithmetic over the live keys.
+__global__ __launch_bounds__(256) void softmax_cols_len_kernel(float* __restrict__ s, int B, int N, int T, const int* __restrict__ live) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= (long)B * T) return;
+  const int nl = min(max(live[0], 0), N), tl = min(max(live[1], 0), T);
+  const int b = (int)(i / T), t = (int)(i % T);
+  float* p = s + (long)b * N * T + t;
+  const int nv = t < tl ? nl : 0;
+  if (nv > 0) {
+    float mx = -INFINITY;
+    for (int n = 0; n < nv; ++n) mx = fmaxf(mx, p[(long)n * T]);
+    float sum = 0.f;
+    for (int n = 0; n < nv; ++n) { const float e = expf(p[(long)n * T] - mx); p[(long)n * T] = e; sum += e; }
+    const float inv = 1.f / sum;
+    for (int n = 0; n < nv; ++n) p[(long)n * T] *= inv;
+  }
+  for (int n = nv; n < N; ++n) p[(long)n * T] = 0.f;
+}
+int ssv_launch_softmax_cols_len(float* s, int B, int N, int T, const int* live, hipStream_t st) {
+  hipLaunchKernelGGL(softmax_cols_len_kernel, dim3(ssv_cdiv((long)B * T, 256)), dim3(256), 0, st, s, B, N, T, live);
+  return ssv_check_launch("softmax_cols_len");
+}
+
 // ---- synthesis step: one workgroup per batch item --------------------------------------------------
 // logits[n] = (sum_c k[c][n] q[c]) / sqrt(d); positions outside [pma, pma+2] are set to -2^32 exactly
 // as the reference does before its softmax (their exp underflows to 0); the new attention column and

@@ -633,6 +633,123 @@ extern "C" int ssv_guided_att_loss_bwd(const float* gaw, int gaw_T, const float*
   return ssv_check_launch("gatt_bwd");
 }
 
+// ---- length masks of the bucketed training step ---------------------------------------------------------
+// A step captured at a bucket shape reads the batch's live lengths from device ints: *live (times `mult` inside SSRN's upsampled
+// stages), clamped to [0, L].  Columns at or past it are exactly zero in every activation and gradient.
+__device__ __forceinline__ int live_cols(const int* __restrict__ live, int mult, int L) {
+  const long v = (long)live[0] * mult;
+  return v <= 0 ? 0 : (v < L ? (int)v : L);
+}
+// x(b, c, t) = 0 for t >= live: only the tail columns are written, nothing is read but the length.  A workgroup owns 8 rows of one item
+// (32 lanes per row walk the tail), grid (ceil(C/8), B): the grid is fixed at capture while the tail is not, and a grid over all L
+// columns made ~10^5 workgroups that mostly exit at once (~24 us per launch at (32, 512, 1300) with nothing to write).
+__global__ __launch_bounds__(256) void mask_cols_kernel(float* __restrict__ x, long bs, int C, int L, const int* __restrict__ live, int mult) {
+  const int c = blockIdx.x * 8 + (threadIdx.x >> 5);
+  if (c >= C) return;
+  float* __restrict__ row = x + blockIdx.y * bs + (long)c * L;
+  for (int t = live_cols(live, mult, L) + (threadIdx.x & 31); t < L; t += 32) row[t] = 0.f;
+}
+extern "C" int ssv_mask_cols(float* x, long x_bs, int B, int C, int L, const int* live, int mult, ssv_stream_t stream) {
+  SSV_CHECK(x && live && B > 0 && B <= 65535 && C > 0 && L > 0 && mult > 0 && x_bs >= (long)C * L, SSV_BAD_SHAPE,
+            "mask_cols: bad argument (B=%d C=%d L=%d mult=%d)", B, C, L, mult);
+  hipLaunchKernelGGL(mask_cols_kernel, dim3(ssv_cdiv(C, 8), B), dim3(256), 0, (hipStream_t)stream, x, x_bs, C, L, live, mult);
+  return ssv_check_launch("mask_cols");
+}
+// Spectrogram losses over the live columns t < mult * live of (B, C, L) tensors; the means divide by B * C * (mult * live), the
+// reference's B*F*T_b (its collate pads to the batch's own longest item, data/dataset.py:187-258).  dy (when given) is the gradient for
+// the seed gscale inside the live region and 0 outside.  Same per-element arithmetic as spec_loss_fused_kernel.
+__global__ __launch_bounds__(256) void spec_loss_len_kernel(const float* __restrict__ y, const float* __restrict__ gt, int C, int L, long n,
+                                                            const int* __restrict__ live, int mult, const float* __restrict__ gscale,
+                                                            float* __restrict__ dy, float* __restrict__ part) {
+  __shared__ float red[4];
+  const int lv = live_cols(live, mult, L);
+  const float inv = lv > 0 ? 1.f / ((float)(n / L) * (float)lv) : 0.f;
+  const float w1 = dy ? gscale[0] * inv : 0.f, w2 = dy ? gscale[1] * inv : 0.f;
+  float s1 = 0.f, s2 = 0.f;
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
+    const int t = (int)(i % L);
+    float d = 0.f;
+    if (t < lv) {
+      const float a = y[i], g = gt[i];
+      s1 += fabsf(g - a);
+      s2 += -g * logf(a + 1e-8f) - (1.f - g) * logf(1.f - a + 1e-8f);
+      const float df = a - g;
+      const float sgn = df > 0.f ? 1.f : (df < 0.f ? -1.f : 0.f);
+      d = w1 * sgn + w2 * (-g / (a + 1e-8f) + (1.f - g) / (1.f - a + 1e-8f));
+    }
+    if (dy) dy[i] = d;
+  }
+  s1 = block_sum256(s1, red);
+  s2 = block_sum256(s2, red);
+  if (threadIdx.x == 0) { part[blockIdx.x] = s1; part[gridDim.x + blockIdx.x] = s2; }
+}
+// out[k] = sum_i part[k*nblk + i] / (rows * lv0 * lv1), lv0 = min(mult * live[0], cap0), lv1 = live1 ? min(live1[0], cap1) : 1; fixed order
+__global__ __launch_bounds__(256) void finish_sums_len_kernel(const float* __restrict__ part, int nblk, int nout, long rows, const int* __restrict__ live0,
+                                                              int mult, int cap0, const int* __restrict__ live1, int cap1, float* __restrict__ out) {
+  __shared__ float red[4];
+  const float den = (float)rows * (float)live_cols(live0, mult, cap0) * (live1 ? (float)live_cols(live1, 1, cap1) : 1.f);
+  for (int k = 0; k < nout; ++k) {
+    float s = 0.f;
+    for (int i = threadIdx.x; i < nblk; i += 256) s += part[(long)k * nblk + i];
+    s = block_sum256(s, red);
+    if (threadIdx.x == 0) out[k] = den > 0.f ? s / den : 0.f;
+  }
+}
+extern "C" int ssv_spec_losses_len(const float* y, const float* gt, int B, int C, int L, const int* live, int mult, const float* gscale,
+                                   float* out, float* dy, void* ws, size_t ws_bytes, ssv_stream_t stream) {
+  SSV_CHECK(y && gt && out && live && B > 0 && C > 0 && L > 0 && mult > 0 && (!dy || gscale), SSV_BAD_SHAPE,
+            "spec_losses_len: bad argument (B=%d C=%d L=%d mult=%d)", B, C, L, mult);
+  const long n = (long)B * C * L;
+  SSV_CHECK(ws && ws_bytes >= ssv_spec_losses_workspace(n), SSV_BAD_SHAPE, "spec_losses_len: workspace too small");
+  const int nblk = (int)((n + 255) / 256 < LOSS_BLOCKS ? (n + 255) / 256 : LOSS_BLOCKS);
+  hipLaunchKernelGGL(spec_loss_len_kernel, dim3(nblk), dim3(256), 0, (hipStream_t)stream, y, gt, C, L, n, live, mult, gscale, dy, (float*)ws);
+  SSV_TRY(ssv_check_launch("spec_loss_len"));
+  hipLaunchKernelGGL(finish_sums_len_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const float*)ws, nblk, 2, (long)B * C, live, mult, L,
+                     (const int*)nullptr, 1, out);
+  return ssv_check_launch("finish_sums_len");
+}
+// Guided-attention loss over the live block n < live[0], t < live[1]: sum(a * gaw) / (B * N_b * T_b); da = gscale[0] * gaw / (B * N_b * T_b)
+// inside the block, 0 outside.
+__global__ __launch_bounds__(256) void gatt_part_len_kernel(const float* __restrict__ a, const float* __restrict__ gaw, int gaw_T,
+                                                            long tot, int N, int T, const int* __restrict__ live, float* __restrict__ part) {
+  __shared__ float red[4];
+  const int nl = live_cols(live, 1, N), tl = live_cols(live + 1, 1, T);
+  float s = 0.f;
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < tot; i += (long)gridDim.x * 256) {
+    const int t = (int)(i % T), n = (int)((i / T) % N);
+    if (n < nl && t < tl) s += a[i] * gaw[(long)n * gaw_T + t];
+  }
+  s = block_sum256(s, red);
+  if (threadIdx.x == 0) part[blockIdx.x] = s;
+}
+__global__ __launch_bounds__(256) void gatt_bwd_len_kernel(const float* __restrict__ gaw, int gaw_T, const float* __restrict__ gscale,
+                                                           float* __restrict__ da, long tot, int B, int N, int T, const int* __restrict__ live) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= tot) return;
+  const int nl = live_cols(live, 1, N), tl = live_cols(live + 1, 1, T);
+  const int t = (int)(i % T), n = (int)((i / T) % N);
+  da[i] = (n < nl && t < tl) ? gscale[0] * gaw[(long)n * gaw_T + t] / ((float)B * (float)nl * (float)tl) : 0.f;
+}
+extern "C" int ssv_guided_att_loss_fwd_len(const float* a, const float* gaw, int gaw_T, float* out, int B, int N, int T, const int* live,
+                                           void* ws, size_t ws_bytes, ssv_stream_t stream) {
+  SSV_CHECK(a && gaw && out && live && B > 0 && N > 0 && T > 0 && gaw_T >= T, SSV_BAD_SHAPE, "guided_att_loss_fwd_len: bad shape B=%d N=%d T=%d gaw_T=%d",
+            B, N, T, gaw_T);
+  SSV_CHECK(ws && ws_bytes >= LOSS_BLOCKS * sizeof(float), SSV_BAD_SHAPE, "guided_att_loss_fwd_len: workspace too small");
+  const long tot = (long)B * N * T;
+  const int nblk = (int)((tot + 255) / 256 < LOSS_BLOCKS ? (tot + 255) / 256 : LOSS_BLOCKS);
+  hipLaunchKernelGGL(gatt_part_len_kernel, dim3(nblk), dim3(256), 0, (hipStream_t)stream, a, gaw, gaw_T, tot, N, T, live, (float*)ws);
+  SSV_TRY(ssv_check_launch("gatt_part_len"));
+  hipLaunchKernelGGL(finish_sums_len_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const float*)ws, nblk, 1, (long)B, live, 1, N, live + 1, T, out);
+  return ssv_check_launch("finish_sums_len");
+}
+extern "C" int ssv_guided_att_loss_bwd_len(const float* gaw, int gaw_T, const float* gscale, float* da, int B, int N, int T, const int* live,
+                                           ssv_stream_t stream) {
+  SSV_CHECK(gaw && gscale && da && live && B > 0 && N > 0 && T > 0 && gaw_T >= T, SSV_BAD_SHAPE, "guided_att_loss_bwd_len: bad shape");
+  const long tot = (long)B * N * T;
+  hipLaunchKernelGGL(gatt_bwd_len_kernel, dim3(ssv_cdiv(tot, 256)), dim3(256), 0, (hipStream_t)stream, gaw, gaw_T, gscale, da, tot, B, N, T, live);
+  return ssv_check_launch("gatt_bwd_len");
+}
+
 // ---- multi-tensor Adam -----------------------------------------------------------------------------------
 // Same arithmetic as torch.optim.Adam's single-tensor path: m = b1 m + (1-b1) g; v = b2 v + (1-b2) g^2;
 // denom = sqrt(v)/sqrt(1-b2^t) + eps; p -= (lr/(1-b1^t)) * m / denom.

@@ -355,8 +355,17 @@ def validate(loader, trainloader, gaw, cfg, model, train_step="train_text2mel"):
     return total / max(n, 1), last
 
 
-def ordinary_train(train_step, train_pattern, cfg, spec_dir=None, resume_checkpoints=None, current_time=None):
-    """Non-adversarial training, train/ordinary.py:130-293.  Under torchrun: data parallel, one rank per GPU (``_distributed``)."""
+def ordinary_train(train_step, train_pattern, cfg, spec_dir=None, resume_checkpoints=None, current_time=None, bucket_stats=None):
+    """Non-adversarial training, train/ordinary.py:130-293.  Under torchrun: data parallel, one rank per GPU (``_distributed``).
+
+    Optional config key LENGTH_BUCKETS ([N, T] pairs for train_text2mel, T values for train_ssrn, each within MAX_TEXT_LEN /
+    MAX_FRAME_NUM): iterations run on ``train.BucketedTrainStep`` -- every batch replays the captured step of the smallest bucket
+    that holds it, with the same losses and updates as the eager step on the unpadded batch; batches of another size or larger
+    than every bucket run eagerly.  Without it every iteration runs eagerly.  ``bucket_stats``: a dict that receives the bucketed step's
+    counters (replays, eager, captures, capture_seconds, pool_bytes) when the run ends."""
+    buckets = cfg.get("LENGTH_BUCKETS")
+    if buckets is not None:
+        train.check_buckets("text2mel" if train_step == "train_text2mel" else "ssrn", buckets, cfg["MAX_TEXT_LEN"], cfg["MAX_FRAME_NUM"])
     rank, world = _distributed(cfg)
     print = _rank0_print(rank)                               # the reference prints from its one process: rank 0 here
     dev = _device()
@@ -382,47 +391,66 @@ def ordinary_train(train_step, train_pattern, cfg, spec_dir=None, resume_checkpo
         if resume_checkpoints is None:
             ddp.broadcast_parameters(0)                      # what DataParallel's replicate does, once instead of per iteration
             opt.refresh_resident_weights()
+    gaw = train.guided_attention_mat(cfg["MAX_TEXT_LEN"], cfg["MAX_FRAME_NUM"], device=dev)
+    bucketed = None
+    if buckets is not None:
+        opt.capturable = True                                # the step count lives on the device (replayed Adam)
+        bucketed = train.BucketedTrainStep("text2mel" if train_step == "train_text2mel" else "ssrn", model, opt, buckets,
+                                           gaw=gaw if train_step == "train_text2mel" else None, ddp=ddp, batch_size=cfg["BATCH_SIZE"])
     src = Prefetcher(BatchSource(cfg, train_step, cfg["BATCH_SIZE"], spec_dir, rank=rank, world=world, pattern=train_pattern), dev)
     val_src = BatchSource(cfg, train_step, 8, spec_dir, seed=7919, pattern=train_pattern, mode="validate")     # batch 8, :200
     if val_src.corpus is None:
         val_src.n_synth = int(cfg.get("SYNTHETIC_VALIDATION_BATCHES", 1))
-    gaw = train.guided_attention_mat(cfg["MAX_TEXT_LEN"], cfg["MAX_FRAME_NUM"], device=dev)
     max_iter = cfg.get("MAX_ITERATIONS")
     history = []
-    while epoch < cfg["MAX_EPOCHS"]:
-        for i, sp in enumerate(src):
-            t0 = time.time()
-            sp = _pad_to_global(sp, world)
-            mel_gt = sp["data_0"].to(dev)
-            if train_step == "train_text2mel":
-                l1, bd, la, att = train.text2mel_step(model, opt, mel_gt, sp["data_1"].to(dev), sp["data_2"].to(dev), gaw, ddp=ddp)
-                terms = (l1, bd, la)
-            else:
-                terms = train.ssrn_step(model, opt, mel_gt, sp["data_1"].to(dev), ddp=ddp)
-            if ddp is not None:
-                terms = ddp.all_reduce_mean(*terms)          # the log shows the global-batch loss, as the reference's gathered outputs do
-            terms = tuple(float(t.detach()) for t in terms)
-            history.append(sum(terms))
-            print("Iteration {}/{} for epoch {}, loss: {} {} global iteration {}".format(
-                i + 1, len(src), epoch + 1, " ".join(str(t) for t in terms), sum(terms), iteration + 1))
-            if iteration % cfg["VAL_EVERY_ITER"] == 0 and iteration > 0 and rank == 0:      # replicas are identical: rank 0 validates and saves
-                model.eval()                                       # train/ordinary.py:264-267
-                loss_val, loss_val_train = validate(val_src, src.source, gaw, cfg, model, train_step)
-                model.train()
-                loss_val_log.append(loss_val)
-                print("Validation loss of No.{} validation: {} on validation set. {} on train set.".format(
-                    iteration // cfg["VAL_EVERY_ITER"], loss_val, loss_val_train))
-                payload = {"epoch": epoch + 1, "iteration": iteration + 1, "model_state_dict": model.state_dict(),
-                           "optimizer_state_dict": opt.state_dict(), "loss_val_log": loss_val_log}
-                _save(os.path.join(save_dir, "{}_iteration_{}.tar.pth".format(train_step[6:], iteration + 1)), payload)
-                if loss_val_log.index(min(loss_val_log)) == len(loss_val_log) - 1:
-                    _save(os.path.join(save_dir, "{}_best_model.tar.pth".format(train_step[6:])), payload)
-            iteration += 1
-            print("Time elapsed {}s".format(time.time() - t0))
-            if max_iter is not None and iteration >= max_iter:
-                return model, history
-        epoch += 1
-    return model, history
+    try:
+        while epoch < cfg["MAX_EPOCHS"]:
+            for i, sp in enumerate(src):
+                t0 = time.time()
+                sp = _pad_to_global(sp, world)
+                mel_gt = sp["data_0"].to(dev)
+                if bucketed is not None:
+                    keys = ("data_1", "data_2") if train_step == "train_text2mel" else ("data_1",)
+                    terms = tuple(bucketed(mel_gt, *[sp[k].to(dev) for k in keys]))
+                elif train_step == "train_text2mel":
+                    l1, bd, la, att = train.text2mel_step(model, opt, mel_gt, sp["data_1"].to(dev), sp["data_2"].to(dev), gaw, ddp=ddp)
+                    terms = (l1, bd, la)
+                else:
+                    terms = train.ssrn_step(model, opt, mel_gt, sp["data_1"].to(dev), ddp=ddp)
+                if ddp is not None:
+                    terms = ddp.all_reduce_mean(*terms)          # the log shows the global-batch loss, as the reference's gathered outputs do
+                terms = tuple(float(t.detach()) for t in terms)
+                history.append(sum(terms))
+                print("Iteration {}/{} for epoch {}, loss: {} {} global iteration {}".format(
+                    i + 1, len(src), epoch + 1, " ".join(str(t) for t in terms), sum(terms), iteration + 1))
+                if iteration % cfg["VAL_EVERY_ITER"] == 0 and iteration > 0 and rank == 0:      # replicas are identical: rank 0 validates and saves
+                    model.eval()                                       # train/ordinary.py:264-267
+                    loss_val, loss_val_train = validate(val_src, src.source, gaw, cfg, model, train_step)
+                    model.train()
+                    loss_val_log.append(loss_val)
+                    print("Validation loss of No.{} validation: {} on validation set. {} on train set.".format(
+                        iteration // cfg["VAL_EVERY_ITER"], loss_val, loss_val_train))
+                    payload = {"epoch": epoch + 1, "iteration": iteration + 1, "model_state_dict": model.state_dict(),
+                               "optimizer_state_dict": opt.state_dict(), "loss_val_log": loss_val_log}
+                    _save(os.path.join(save_dir, "{}_iteration_{}.tar.pth".format(train_step[6:], iteration + 1)), payload)
+                    if loss_val_log.index(min(loss_val_log)) == len(loss_val_log) - 1:
+                        _save(os.path.join(save_dir, "{}_best_model.tar.pth".format(train_step[6:])), payload)
+                iteration += 1
+                print("Time elapsed {}s".format(time.time() - t0))
+                if max_iter is not None and iteration >= max_iter:
+                    return model, history
+            epoch += 1
+        return model, history
+    finally:
+        if bucketed is not None:                             # the captured graphs and the private gradient arena go with the run
+            if bucket_stats is not None:
+                bucket_stats.update(_bucket_stats(bucketed))
+            bucketed.close()
+
+
+def _bucket_stats(b):
+    return {"replays": b.replays, "eager": b.eager, "captures": b.captures, "capture_seconds": b.capture_seconds,
+            "pool_bytes": dict(b.pool_bytes)}
 
 
 def adversarial_train(train_step, train_pattern, cfg, spec_dir=None, resume_checkpoints=None, current_time=None):

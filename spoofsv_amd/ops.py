@@ -60,6 +60,29 @@ def _ws(nbytes, device):
     return torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=device)
 
 
+class Live:
+    """The live length of a stack in a length-masked step (a batch padded to a bucket shape): entry ``index`` of the int32 device tensor
+    ``lens``, times ``mult`` (SSRN's upsampled stages).  The kernels read it when they run, so one captured hipGraph serves every batch
+    that fits its bucket.  Columns at or past it are kept exactly 0 in the layer's output and in the gradient its backward receives."""
+    __slots__ = ("lens", "index", "mult")
+
+    def __init__(self, lens, index=0, mult=1):
+        if lens.dtype != torch.int32 or not lens.is_cuda or lens.dim() != 1 or not 0 <= index < lens.numel():
+            raise RuntimeError("Live: lens must be a 1-D int32 device tensor with an entry %d" % index)
+        self.lens, self.index, self.mult = lens, int(index), int(mult)
+
+    def ptr(self):
+        return ctypes.c_void_p(self.lens.data_ptr() + 4 * self.index)
+
+
+def _mask_cols(t, bs, live):
+    """Zero the columns of ``t`` (B, C, L) at or past ``live`` in place (one launch; no-op for ``live=None``)."""
+    if live is None:
+        return
+    B, C, L = t.shape
+    _lib.call("ssv_mask_cols", _p(t), bs, B, C, L, live.ptr(), live.mult, _stream())
+
+
 # ------------------------------------------------------------------------------------------- split-fp16 operand scales
 # include/ssv_hip.h, "Operand scales (mode 2)": a kernel that reads an fp32 tensor as an MFMA operand needs a list of partial
 # maxima of |x| (n entries per batch item).  The LayerNorm / gate kernels write one for their output as a by-product; it
@@ -289,7 +312,7 @@ class HighwayConvFn(torch.autograd.Function):
     """highwayConv.forward, models/TTSModel.py:63-84 (conv -> 2x LayerNorm over channels -> gate)."""
 
     @staticmethod
-    def forward(ctx, x, w, bias, g1, b1, g2, b2, k, dilation, causal, x_amax=None, y_amax=None):
+    def forward(ctx, x, w, bias, g1, b1, g2, b2, k, dilation, causal, x_amax=None, y_amax=None, live=None):
         x, xbs = _act3(x, "highwayConv input")
         B, C, L = x.shape
         w, bias, g1, b1, g2, b2 = map(_c, (w, bias, g1, b1, g2, b2))
@@ -303,9 +326,11 @@ class HighwayConvFn(torch.autograd.Function):
         ws = _ws(nb, x.device)
         _lib.call("ssv_highway_conv1d_fwd", _p(x), xbs, *_an(x_amax), _p(w), resident.lookup(w), _p(bias), _p(g1), _p(b1), _p(g2), _p(b2),
                   _p(h), _p(stats), _p(y), C * L, _p(y_amax), B, C, L, k, dilation, int(causal), _p(ws), nb, _stream())
+        _mask_cols(y, C * L, live)
         if train:
             ctx.save_for_backward(x, w, g1, b1, g2, b2, h, stats)
             ctx.x_amax = x_amax
+            ctx.live = live
             ctx.cfg = (k, dilation, int(causal))
             ctx.bias_ref = bias           # only its address is used (gradient-arena lookup); not needed by the kernels
         return y
@@ -316,6 +341,7 @@ class HighwayConvFn(torch.autograd.Function):
         k, dilation, causal = ctx.cfg
         x, xbs = _act3(x)
         dy, dybs = _act3(dy, "highwayConv grad")
+        _mask_cols(dy, dybs, ctx.live)
         B, C, L = x.shape
         dx = torch.empty((B, C, L), dtype=_F32, device=x.device)
         # parameter gradients go straight into the data-parallel gradient arena when the model has one (gradarena.py)
@@ -336,13 +362,13 @@ class HighwayConvFn(torch.autograd.Function):
             _lib.call("ssv_highway_conv1d_bwd_data", _p(dy), dybs, _p(x), xbs, _p(w), resident.lookup(w), _p(g1), _p(b1), _p(g2), _p(b2),
                       _p(h), _p(stats), _p(dx), C * L, _p(dh), _p(dh_amax), _p(part), B, C, L, k, dilation, causal, _p(ws), nb, _stream())
             _DEFER.add(dh, 2 * C * L, x, xbs, dw, part, pg, k, dilation, causal, 6 * C, rows, dh_amax, x_amax)
-            return (dx, dw, pg[4:6].reshape(2 * C), pg[0], pg[1], pg[2], pg[3]) + (None,) * 5
+            return (dx, dw, pg[4:6].reshape(2 * C), pg[0], pg[1], pg[2], pg[3]) + (None,) * 6
         nb = _lib.query("ssv_highway_conv1d_bwd_workspace", B, C, L, k)
         ws = _ws(nb, x.device)
         _lib.call("ssv_highway_conv1d_bwd", _p(dy), dybs, _p(x), xbs, *_an(ctx.x_amax), _p(w), resident.lookup(w), _p(g1), _p(b1), _p(g2), _p(b2),
                   _p(h), _p(stats), _p(dx), C * L, _p(dw), _p(pg), B, C, L, k, dilation, causal,
                   _p(ws), nb, _stream())
-        return (dx, dw, pg[4:6].reshape(2 * C), pg[0], pg[1], pg[2], pg[3]) + (None,) * 5
+        return (dx, dw, pg[4:6].reshape(2 * C), pg[0], pg[1], pg[2], pg[3]) + (None,) * 6
 
 
 # ------------------------------------------------------------------------------------------- conv
@@ -392,7 +418,7 @@ class PointwiseConvLnActFn(torch.autograd.Function):
     """
 
     @staticmethod
-    def forward(ctx, x, w, bias, gamma, beta, s, act, x_amax=None, y_amax=None):
+    def forward(ctx, x, w, bias, gamma, beta, s, act, x_amax=None, y_amax=None, live=None):
         x, xbs = _act3(x, "conv input")
         B, Cin, L = x.shape
         w, bias, gamma, beta = map(_c, (w, bias, gamma, beta))
@@ -410,9 +436,11 @@ class PointwiseConvLnActFn(torch.autograd.Function):
         ws = _ws(nb, x.device)
         _lib.call("ssv_pointwise_conv_ln_act_fwd", _p(x), xbs, *_an(x_amax), _p(w), resident.lookup(w), _p(bias), _p(sb), _p(gamma), _p(beta),
                   _p(pre), _p(stats), _p(y), Cout * L, _p(y_amax), B, Cin, Cout, L, act, _p(ws), nb, _stream())
+        _mask_cols(y, Cout * L, live)
         if train:
             ctx.save_for_backward(x, w, gamma, beta, pre, stats)
             ctx.x_amax = x_amax
+            ctx.live = live
             ctx.act = act
             ctx.bias_ref = bias
             ctx.has_s = s is not None
@@ -424,6 +452,7 @@ class PointwiseConvLnActFn(torch.autograd.Function):
         x, w, gamma, beta, pre, stats = ctx.saved_tensors
         x, xbs = _act3(x)
         dy, dybs = _act3(dy, "grad")
+        _mask_cols(dy, dybs, ctx.live)
         B, Cin, L = x.shape
         Cout = w.shape[0]
         pg = gradarena.grad_block((gamma, beta, ctx.bias_ref), 3, Cout, x.device)
@@ -443,12 +472,12 @@ class PointwiseConvLnActFn(torch.autograd.Function):
             _lib.call("ssv_pointwise_conv_ln_act_bwd_data", _p(dy), dybs, _p(w), resident.lookup(w), _p(gamma), _p(beta), _p(pre), _p(stats),
                       _p(dx), Cin * L, _p(ds), _p(dpre), _p(dpre_amax), _p(part), B, Cin, Cout, L, ctx.act, _p(ws), nb, _stream())
             _DEFER.add(dpre, Cout * L, x, xbs, dw, part, pg, 1, 1, 0, 3 * Cout, rows, dpre_amax, x_amax)
-            return dx, dw, pg[2], pg[0], pg[1], ds, None, None, None
+            return dx, dw, pg[2], pg[0], pg[1], ds, None, None, None, None
         nb = _lib.query("ssv_pointwise_conv_ln_act_bwd_workspace", B, Cin, Cout, L)
         ws = _ws(nb, x.device)
         _lib.call("ssv_pointwise_conv_ln_act_bwd", _p(dy), dybs, _p(x), xbs, *_an(ctx.x_amax), _p(w), resident.lookup(w), _p(gamma), _p(beta), _p(pre), _p(stats),
                   _p(dx), Cin * L, _p(dw), _p(pg), _p(ds), B, Cin, Cout, L, ctx.act, _p(ws), nb, _stream())
-        return dx, dw, pg[2], pg[0], pg[1], ds, None, None, None
+        return dx, dw, pg[2], pg[0], pg[1], ds, None, None, None, None
 
 
 class Conv1dFn(torch.autograd.Function):
@@ -927,7 +956,7 @@ class TextEmbedFn(torch.autograd.Function):
     """textEmbedding.forward, models/TTSModel.py:25-35: one-hot + Linear == column gather + bias."""
 
     @staticmethod
-    def forward(ctx, ids, w, bias):
+    def forward(ctx, ids, w, bias, live=None):
         _dev(ids, "text ids")
         ids = ids.long().contiguous()
         B, one, N = ids.shape
@@ -935,7 +964,9 @@ class TextEmbedFn(torch.autograd.Function):
         E, V = w.shape
         y = torch.empty((B, E, N), dtype=_F32, device=w.device)
         _lib.call("ssv_text_embed_fwd", _p(ids), _p(w), _p(bias), _p(y), B, N, E, V, _stream())
+        _mask_cols(y, E * N, live)
         if _needs_grad(ctx):
+            ctx.live = live
             ctx.save_for_backward(ids)
             ctx.dims = (B, N, E, V)
             ctx.refs = (w, bias)
@@ -946,10 +977,11 @@ class TextEmbedFn(torch.autograd.Function):
         (ids,) = ctx.saved_tensors
         B, N, E, V = ctx.dims
         dy = _c(dy)
+        _mask_cols(dy, E * N, ctx.live)
         dw = gradarena.grad_like(ctx.refs[0])
         db = gradarena.grad_like(ctx.refs[1])
         _lib.call("ssv_text_embed_bwd", _p(ids), _p(dy), _p(dw), _p(db), B, N, E, V, _stream())
-        return None, dw, db
+        return None, dw, db, None
 
 
 # ------------------------------------------------------------------------------------------- attention
@@ -958,7 +990,7 @@ class AttentionTrainFn(torch.autograd.Function):
     :138-139); q: (B, d, T).  Returns (cat(R, Q) (B, 2d, T), A (B, N, T))."""
 
     @staticmethod
-    def forward(ctx, kv, q):
+    def forward(ctx, kv, q, live=None):
         kv, kvbs = _act3(kv, "K|V")
         q, qbs = _act3(q, "Q")
         B, d2, N = kv.shape
@@ -969,7 +1001,10 @@ class AttentionTrainFn(torch.autograd.Function):
         rq = torch.empty((B, 2 * d, T), dtype=_F32, device=q.device)
         k_ptr = ctypes.c_void_p(kv.data_ptr())
         v_ptr = ctypes.c_void_p(kv.data_ptr() + 4 * d * N)
-        _lib.call("ssv_attention_train_fwd_rq", k_ptr, v_ptr, kvbs, _p(q), qbs, _p(a), _p(rq), 2 * d * T, B, d, N, T, _stream())
+        if live is None:
+            _lib.call("ssv_attention_train_fwd_rq", k_ptr, v_ptr, kvbs, _p(q), qbs, _p(a), _p(rq), 2 * d * T, B, d, N, T, _stream())
+        else:         # live: (N_b, T_b) at lens[index], lens[index + 1]
+            _lib.call("ssv_attention_train_fwd_rq_len", k_ptr, v_ptr, kvbs, _p(q), qbs, _p(a), _p(rq), 2 * d * T, B, d, N, T, live.ptr(), _stream())
         if _needs_grad(ctx):
             ctx.save_for_backward(kv, q, a)
         return rq, a
@@ -994,7 +1029,7 @@ class AttentionTrainFn(torch.autograd.Function):
                   ctypes.c_void_p(kv.data_ptr()), ctypes.c_void_p(kv.data_ptr() + 4 * d * N), kvbs, _p(q), qbs, _p(a),
                   ctypes.c_void_p(dkv.data_ptr()), ctypes.c_void_p(dkv.data_ptr() + 4 * d * N), 2 * d * N, _p(dq), d * T,
                   B, d, N, T, _p(ws), nb, _stream())
-        return dkv, dq
+        return dkv, dq, None
 
 
 def attention_step(kv, q, pma, a_buf, col):
@@ -1047,7 +1082,7 @@ class DeconvK2S2Fn(torch.autograd.Function):
     """nn.ConvTranspose1d(C, C, kernel_size=2, stride=2), models/TTSModel.py:309,314."""
 
     @staticmethod
-    def forward(ctx, x, w, bias, x_amax=None, y_amax=None):
+    def forward(ctx, x, w, bias, x_amax=None, y_amax=None, live=None):
         x, xbs = _act3(x, "deconv input")
         B, Cin, L = x.shape
         w, bias = _c(w), _c(bias)
@@ -1061,7 +1096,9 @@ class DeconvK2S2Fn(torch.autograd.Function):
         # y's operand-scale list (y_amax, (B, 64)) for the highway layer that follows (before: two stride-2 products, a per-call weight split, an ssv_absmax over y)
         _lib.call("ssv_deconv1d_k2s2_fwd", _p(x), xbs, *_an(x_amax), _p(w), resident.lookup(w.view(Cin, 2 * Cout, 1)), _p(bias), _p(y), Cout * 2 * L,
                   _p(y_amax), 64, B, Cin, Cout, L, _p(ws), nb, _stream())
+        _mask_cols(y, Cout * 2 * L, live)           # (live: the OUTPUT's length, 2 T_b)
         if _needs_grad(ctx):
+            ctx.live = live
             ctx.save_for_backward(x, w)
             ctx.bias_ref = bias
             ctx.x_amax = x_amax           # (a saved tensor comes back without its Python attributes: the list travels beside it)
@@ -1072,6 +1109,7 @@ class DeconvK2S2Fn(torch.autograd.Function):
         x, w = ctx.saved_tensors
         x, xbs = _act3(x)
         dy, dybs = _act3(dy, "grad")
+        _mask_cols(dy, dybs, ctx.live)
         B, Cin, L = x.shape
         Cout = w.shape[1]
         dx = torch.empty((B, Cin, L), dtype=_F32, device=x.device)
@@ -1095,10 +1133,10 @@ class DeconvK2S2Fn(torch.autograd.Function):
             x_am = (ctx.x_amax if ctx.x_amax is not None else amax_of(x)) if f16 else None
             _conv_bwd_weight(x, xbs, du, 2 * Cout * L, (Cin, 2 * Cout, 1), 1, 1, 0, dw.view(Cin, 2 * Cout, 1), x_am, du_am)
             _lib.call("ssv_bias_grad", _p(dy), dybs, _p(db), B, Cout, 2 * L, _stream())
-            return dx, dw, db, None, None
+            return dx, dw, db, None, None, None
         _lib.call("ssv_deconv1d_k2s2_bwd", _p(dy), dybs, None, 0, _p(x), xbs, _p(w), _p(dx), Cin * L, _p(dw), _p(db),
                   B, Cin, Cout, L, _p(ws), nb, _stream())
-        return dx, dw, db, None, None
+        return dx, dw, db, None, None, None
 
 
 # ------------------------------------------------------------------------------------------- losses
@@ -1111,7 +1149,7 @@ class SpecLossFn(torch.autograd.Function):
     separate backward kernel and drops the stored dy."""
 
     @staticmethod
-    def forward(ctx, y, gt, seed=None):
+    def forward(ctx, y, gt, seed=None, live=None):
         y, gt = _c(y), _c(gt)
         if y.shape != gt.shape:
             raise RuntimeError("spec loss: prediction %s vs target %s" % (tuple(y.shape), tuple(gt.shape)))
@@ -1120,14 +1158,22 @@ class SpecLossFn(torch.autograd.Function):
         nb = _lib.query("ssv_spec_losses_workspace", n)
         ws = _ws(nb, y.device)
         ctx.fused = None
+        ctx.live = live
+        if live is not None and y.dim() != 3:
+            raise RuntimeError("spec loss: a length-masked loss needs (B, C, L) tensors, got %s" % (tuple(y.shape),))
         if seed is not None and ctx.needs_input_grad[0]:
             if seed.dtype != _F32 or seed.numel() != 2 or seed.device != y.device or not seed.is_contiguous():
                 raise RuntimeError("spec loss: the promised gradient seed must be a contiguous float32 2-vector on the prediction's device")
             dy = torch.empty_like(y)
-            _lib.call("ssv_spec_losses_fwd_bwd", _p(y), _p(gt), n, _p(seed), _p(out), _p(dy), _p(ws), nb, _stream())
+            if live is None:
+                _lib.call("ssv_spec_losses_fwd_bwd", _p(y), _p(gt), n, _p(seed), _p(out), _p(dy), _p(ws), nb, _stream())
+            else:
+                _lib.call("ssv_spec_losses_len", _p(y), _p(gt), *y.shape, live.ptr(), live.mult, _p(seed), _p(out), _p(dy), _p(ws), nb, _stream())
             ctx.fused = (dy, seed, seed._version)
-        else:
+        elif live is None:
             _lib.call("ssv_spec_losses_fwd", _p(y), _p(gt), n, _p(out), _p(ws), nb, _stream())
+        else:
+            _lib.call("ssv_spec_losses_len", _p(y), _p(gt), *y.shape, live.ptr(), live.mult, None, _p(out), None, _p(ws), nb, _stream())
         ctx.save_for_backward(y, gt)
         return out
 
@@ -1136,19 +1182,26 @@ class SpecLossFn(torch.autograd.Function):
         y, gt = ctx.saved_tensors
         f = ctx.fused
         if f is not None and gout is f[1] and gout._version == f[2]:
-            return f[0], None, None
+            return f[0], None, None, None
         ctx.fused = None
         gout = _c(gout)
         dy = torch.empty_like(y)
-        _lib.call("ssv_spec_losses_bwd", _p(y), _p(gt), y.numel(), _p(gout), _p(dy), _stream())
-        return dy, None, None
+        live = ctx.live
+        if live is None:
+            _lib.call("ssv_spec_losses_bwd", _p(y), _p(gt), y.numel(), _p(gout), _p(dy), _stream())
+        else:           # the masked pass again, for its dy (the two loss values it also writes go to a scratch vector)
+            nb = _lib.query("ssv_spec_losses_workspace", y.numel())
+            scratch = torch.empty((2,), dtype=_F32, device=y.device)
+            _lib.call("ssv_spec_losses_len", _p(y), _p(gt), *y.shape, live.ptr(), live.mult, _p(gout), _p(scratch), _p(dy),
+                      _p(_ws(nb, y.device)), nb, _stream())
+        return dy, None, None, None
 
 
 class GuidedAttLossFn(torch.autograd.Function):
     """train/ordinary.py:232-234: sum(A * W[:N, :T]) / (B*N*T) as a 1-vector."""
 
     @staticmethod
-    def forward(ctx, a, gaw):
+    def forward(ctx, a, gaw, live=None):
         a, gaw = _c(a), _c(gaw)
         B, N, T = a.shape
         if gaw.shape[0] < N or gaw.shape[1] < T:
@@ -1156,7 +1209,11 @@ class GuidedAttLossFn(torch.autograd.Function):
         out = torch.empty((1,), dtype=_F32, device=a.device)
         nb = _lib.query("ssv_guided_att_loss_workspace", B, N, T)
         ws = _ws(nb, a.device)
-        _lib.call("ssv_guided_att_loss_fwd", _p(a), _p(gaw), gaw.shape[1], _p(out), B, N, T, _p(ws), nb, _stream())
+        if live is None:
+            _lib.call("ssv_guided_att_loss_fwd", _p(a), _p(gaw), gaw.shape[1], _p(out), B, N, T, _p(ws), nb, _stream())
+        else:         # live: (N_b, T_b) at lens[index], lens[index + 1]
+            _lib.call("ssv_guided_att_loss_fwd_len", _p(a), _p(gaw), gaw.shape[1], _p(out), B, N, T, live.ptr(), _p(ws), nb, _stream())
+        ctx.live = live
         ctx.save_for_backward(gaw)
         ctx.dims = (B, N, T)
         return out
@@ -1167,8 +1224,11 @@ class GuidedAttLossFn(torch.autograd.Function):
         B, N, T = ctx.dims
         gout = _c(gout)
         da = torch.empty((B, N, T), dtype=_F32, device=gaw.device)
-        _lib.call("ssv_guided_att_loss_bwd", _p(gaw), gaw.shape[1], _p(gout), _p(da), B, N, T, _stream())
-        return da, None
+        if ctx.live is None:
+            _lib.call("ssv_guided_att_loss_bwd", _p(gaw), gaw.shape[1], _p(gout), _p(da), B, N, T, _stream())
+        else:
+            _lib.call("ssv_guided_att_loss_bwd_len", _p(gaw), gaw.shape[1], _p(gout), _p(da), B, N, T, ctx.live.ptr(), _stream())
+        return da, None, None
 
 
 # ------------------------------------------------------------------------------------------- functional
@@ -1177,22 +1237,22 @@ def _bf3_shape(x):
     return x.dim() == 3 and x.shape[0] * x.shape[2] >= 128
 
 
-def highway_conv1d(x, w, bias, g1, b1, g2, b2, k, dilation, causal):
+def highway_conv1d(x, w, bias, g1, b1, g2, b2, k, dilation, causal, live=None):
     if not (_f16() and _bf3_shape(x)):
-        return HighwayConvFn.apply(x, w, bias, g1, b1, g2, b2, k, dilation, causal)
+        return HighwayConvFn.apply(x, w, bias, g1, b1, g2, b2, k, dilation, causal, None, None, live)
     ya = _amax_out(x.shape[0], x.shape[2], x.device)
-    return _tag(HighwayConvFn.apply(x, w, bias, g1, b1, g2, b2, k, dilation, causal, amax_of(x), ya), ya)
+    return _tag(HighwayConvFn.apply(x, w, bias, g1, b1, g2, b2, k, dilation, causal, amax_of(x), ya, live), ya)
 
 
 RELU_TAP = None      # diagnostics / tests: a list that receives (y > 0) of every fused-ReLU output, in call order
 
 
-def pointwise_conv_ln_act(x, w, bias, gamma, beta, s=None, act=0):
+def pointwise_conv_ln_act(x, w, bias, gamma, beta, s=None, act=0, live=None):
     if not (_f16() and _bf3_shape(x)):
-        y = PointwiseConvLnActFn.apply(x, w, bias, gamma, beta, s, act)
+        y = PointwiseConvLnActFn.apply(x, w, bias, gamma, beta, s, act, None, None, live)
     else:
         ya = _amax_out(x.shape[0], x.shape[2], x.device)
-        y = _tag(PointwiseConvLnActFn.apply(x, w, bias, gamma, beta, s, act, amax_of(x), ya), ya)
+        y = _tag(PointwiseConvLnActFn.apply(x, w, bias, gamma, beta, s, act, amax_of(x), ya, live), ya)
     if RELU_TAP is not None and act == 1:
         RELU_TAP.append(y.detach() > 0)
     return y
@@ -1204,20 +1264,20 @@ def conv1d(x, w, bias, k=1, dilation=1, causal=False):
     return Conv1dFn.apply(x, w, bias, k, dilation, causal, amax_of(x))
 
 
-def text_embed(ids, w, bias):
-    return TextEmbedFn.apply(ids, w, bias)
+def text_embed(ids, w, bias, live=None):
+    return TextEmbedFn.apply(ids, w, bias, live)
 
 
-def attention_train(kv, q):
-    return AttentionTrainFn.apply(kv, q)
+def attention_train(kv, q, live=None):
+    return AttentionTrainFn.apply(kv, q, live)
 
 
-def deconv1d_k2s2(x, w, bias):
+def deconv1d_k2s2(x, w, bias, live=None):
     resident.mark_transposed(w)          # the weight of a transposed convolution: its planes are kept for the 1x1 view
     if not (_f16() and _bf3_shape(x)):
-        return DeconvK2S2Fn.apply(x, w, bias)
+        return DeconvK2S2Fn.apply(x, w, bias, None, None, live)
     ya = torch.empty((x.shape[0], 64), dtype=_F32, device=x.device)
-    return _tag(DeconvK2S2Fn.apply(x, w, bias, amax_of(x), ya), ya)
+    return _tag(DeconvK2S2Fn.apply(x, w, bias, amax_of(x), ya, live), ya)
 
 
 def spec_losses(y, gt):
@@ -1225,15 +1285,15 @@ def spec_losses(y, gt):
     return out[0], out[1]
 
 
-def spec_losses_vec(y, gt, seed=None):
+def spec_losses_vec(y, gt, seed=None, live=None):
     """(l1, binary divergence) as ONE 2-vector: a training step seeds its backward with a constant gradient vector for it instead of
     summing two selected scalars (each select's backward is a zeros + a scatter + an add of two 2-vectors: tiny launches in a row between
     the end of the forward and the start of the backward).  ``seed``: that vector, when the caller already has it (see SpecLossFn)."""
-    return SpecLossFn.apply(y, gt, seed)
+    return SpecLossFn.apply(y, gt, seed, live)
 
 
-def guided_att_loss_vec(a, gaw):
-    return GuidedAttLossFn.apply(a, gaw)
+def guided_att_loss_vec(a, gaw, live=None):
+    return GuidedAttLossFn.apply(a, gaw, live)
 
 
 def guided_att_loss(a, gaw):

@@ -19,7 +19,7 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
-from . import _lib, ops
+from . import _lib, ops, tts
 from . import resident as _resident
 from .ops import _p, _stream
 
@@ -525,7 +525,7 @@ class PhasedStep:
                 self._eager()
         torch.cuda.current_stream().wait_stream(s)
         torch.cuda.synchronize()
-        pool = torch.cuda.graph_pool_handle()
+        pool = self.pool = torch.cuda.graph_pool_handle()
         plan, i = [], 0
         while i < len(self.phases):
             kind, fn = self.phases[i]
@@ -577,13 +577,16 @@ class TrainStep:
     segments of ``tts.ddp_plan`` and every gradient bucket's all-reduce is started right after its segment, overlapping the
     remaining segments; Adam follows the last collective.  ``out`` holds the iteration's loss terms (device scalars)."""
 
-    def __init__(self, kind, model, opt, batch=None, gaw=None, ddp=None, graph=False, defer_wgrad=False):
+    def __init__(self, kind, model, opt, batch=None, gaw=None, ddp=None, graph=False, defer_wgrad=False, lens=None):
         self.kind, self.model, self.opt, self.gaw, self.ddp = kind, model, opt, gaw, ddp
+        # lens: int32 device tensor of the batch's own maxima -- (N_b, T_b) for Text2Mel, (T_b,) for SSRN -- when the batch is padded to a
+        # larger shape (BucketedTrainStep): the step then computes what the unpadded batch would (tts.live_lengths)
+        self.lens = lens
         # weight gradients of equal-shaped layers batched into one launch per backward segment (ops.DeferredWgrad)
         self.defer = ops.DeferredWgrad() if defer_wgrad else None
         self.static = [b.clone() for b in batch] if (graph and batch is not None) else None
         self.batch = self.static if self.static is not None else batch
-        self.out = self.att = None
+        self.out = self.att = self.pred = None          # loss terms, attention and prediction of the last iteration (detached)
         self._seeds = {}              # (entries, value, device) -> constant gradient vector that seeds the backward
         self.loss_log = None          # a list: receives the loss terms of every EAGERLY executed iteration (warm-up; not replays)
         seg = ddp is not None and ddp.arena is not None
@@ -627,24 +630,27 @@ class TrainStep:
 
         def seed(v):
             return (v, seedvec(v.numel(), v))
+        masked = self.lens is not None
+        live = (lambda: tts.live_lengths(self.model, self.lens)) if masked else contextlib.nullcontext
         if self.kind == "text2mel":
             mel, text, spk = self.batch
-            with _cuts_installed(self.model, self.cuts):
+            with _cuts_installed(self.model, self.cuts), live():
                 pred, att = self.model(shift_right(mel), text, spk)
-            lv, av = ops.spec_losses_vec(pred, mel, seedvec(2, pred)), ops.guided_att_loss_vec(att, self.gaw)
+            lv = ops.spec_losses_vec(pred, mel, seedvec(2, pred), ops.Live(self.lens, 1) if masked else None)
+            av = ops.guided_att_loss_vec(att, self.gaw, ops.Live(self.lens, 0) if masked else None)
             lvd, avd = lv.detach(), av.detach()
-            self.out, self.att = (lvd[0], lvd[1], avd[0]), att.detach()
+            self.out, self.att, self.pred = (lvd[0], lvd[1], avd[0]), att.detach(), pred.detach()
             if "dec_in" in self.cuts.rec:
                 segs = backward_segments(self.cuts, [seed(lv)], {"dec_in": [seed(av)]}, self.ddp, self.defer)
             else:
                 segs = backward_segments(self.cuts, [seed(lv), seed(av)], None, self.ddp, self.defer)
         else:
             mel, lin = self.batch
-            with _cuts_installed(self.model, self.cuts):
+            with _cuts_installed(self.model, self.cuts), live():
                 pred = self.model(mel)
-            lv = ops.spec_losses_vec(pred, lin, seedvec(2, pred))          # (the seed is known: the loss's forward and backward share one pass)
+            lv = ops.spec_losses_vec(pred, lin, seedvec(2, pred), ops.Live(self.lens, 0, 4) if masked else None)   # (the seed is known: the loss's forward and backward share one pass)
             lvd = lv.detach()
-            self.out = (lvd[0], lvd[1])
+            self.out, self.pred = (lvd[0], lvd[1]), pred.detach()
             segs = backward_segments(self.cuts, [seed(lv)], None, self.ddp, self.defer)
         self._segs = segs
         if self.loss_log is not None and not torch.cuda.is_current_stream_capturing():
@@ -694,6 +700,197 @@ def text2mel_step(model, optimizer, mel_gt, text_id, spk_emb, gaw, ddp=None):
 def ssrn_step(model, optimizer, mel_gt, lin_gt, ddp=None):
     """One non-adversarial SSRN iteration (train/ordinary.py:240-254), eagerly."""
     return TrainStep("ssrn", model, optimizer, [mel_gt, lin_gt], None, ddp, graph=False)()
+
+
+def check_buckets(kind, buckets, max_text_len=None, max_frame_num=None):
+    """Validated, sorted bucket list: [N, T] pairs for "text2mel", T values for "ssrn" (tuples ``(N, T)`` / ``(T,)``).  Refuses
+    malformed entries, non-positive sizes, duplicates, and sizes above the configured maxima MAX_TEXT_LEN / MAX_FRAME_NUM."""
+    if kind not in ("text2mel", "ssrn"):
+        raise ValueError("buckets: kind must be 'text2mel' or 'ssrn', not %r" % (kind,))
+    if isinstance(buckets, (str, bytes)) or not hasattr(buckets, "__iter__"):
+        raise ValueError("buckets: a list of %s, got %r" % ("[N, T] pairs" if kind == "text2mel" else "T values", buckets))
+    out = []
+    for b in buckets:
+        if kind == "text2mel":
+            if isinstance(b, (str, bytes)) or not hasattr(b, "__len__") or len(b) != 2:
+                raise ValueError("buckets: a Text2Mel bucket is an [N, T] pair, got %r" % (b,))
+            t = tuple(b)
+        else:
+            t = tuple(b) if hasattr(b, "__len__") and not isinstance(b, (str, bytes)) else (b,)
+            if len(t) != 1:
+                raise ValueError("buckets: an SSRN bucket is one frame count T, got %r" % (b,))
+        if not all(isinstance(v, (int, np.integer)) and not isinstance(v, bool) and v > 0 for v in t):
+            raise ValueError("buckets: sizes must be positive integers, got %r" % (b,))
+        t = tuple(int(v) for v in t)
+        caps = (max_text_len, max_frame_num) if kind == "text2mel" else (max_frame_num,)
+        for v, cap, what in zip(t, caps, ("MAX_TEXT_LEN", "MAX_FRAME_NUM") if kind == "text2mel" else ("MAX_FRAME_NUM",)):
+            if cap is not None and v > cap:
+                raise ValueError("buckets: %r exceeds %s = %d" % (b, what, cap))
+        out.append(t)
+    if not out:
+        raise ValueError("buckets: empty list")
+    if len(set(out)) != len(out):
+        raise ValueError("buckets: duplicate entries in %r" % (list(buckets),))
+    return sorted(out, key=lambda t: (int(np.prod(t)), t))
+
+
+def pick_bucket(buckets, need):
+    """The smallest bucket (fewest padded elements, the list order of ``check_buckets``) that holds ``need`` ((N_b, T_b) or (T_b,)),
+    or None."""
+    for b in buckets:
+        if all(n <= c for n, c in zip(need, b)):
+            return b
+    return None
+
+
+def _pad_into(dst, src):
+    """dst (bucket shape) = src zero-padded along the last axis."""
+    L = src.shape[-1]
+    dst[..., :L].copy_(src, non_blocking=True)
+    if L < dst.shape[-1]:
+        dst[..., L:].zero_()
+
+
+class BucketedTrainStep:
+    """Non-adversarial iterations of ragged corpus batches on captured, replayed steps: one ``TrainStep(graph=True)`` per length
+    bucket -- (N, T) for ``kind`` "text2mel", (T,) for "ssrn" -- captured on the first batch that falls into it.  A batch runs in the
+    smallest bucket that holds its own maxima: it is copied into the bucket's static buffers with the tail columns zeroed, its maxima
+    are written to the step's device ints (``TrainStep.lens``), and the graph is replayed; the length-masked kernels make that
+    compute what the unpadded batch would (tts.live_lengths).  Batches larger than every bucket, and batches whose size differs
+    from the bucket's (the reference's partial last batch, drop_last=False), run eagerly as ``text2mel_step`` / ``ssrn_step`` do.
+
+    The warm-up iterations of a capture do not count: weights and optimizer state are put back afterwards.  Gradients live in a
+    gradient arena (``ddp``, or a one-rank ``DataParallelRanks(model=...)`` made here) so that every bucket's graph and every eager
+    step hand the optimizer the same gradient addresses.  ``opt`` must be ``FusedAdam(capturable=True)``.  ``batch_size``: the B a
+    bucket is captured at (default: the first batch that reaches it).  Counters: ``replays``, ``eager``, ``captures``,
+    ``capture_seconds``; ``pool_bytes[bucket]`` = device memory the capture kept (its activation pool and static buffers)."""
+
+    def __init__(self, kind, model, opt, buckets, gaw=None, ddp=None, defer_wgrad=True, batch_size=None):
+        if not getattr(opt, "capturable", False):
+            raise ValueError("BucketedTrainStep needs FusedAdam(capturable=True)")
+        if kind == "text2mel" and gaw is None:
+            raise ValueError("BucketedTrainStep('text2mel') needs the guided-attention weights gaw")
+        if ddp is not None and ddp.arena is None:
+            raise ValueError("BucketedTrainStep needs an arena DataParallelRanks(model=...) (see TrainStep)")
+        self.kind, self.model, self.opt, self.gaw = kind, model, opt, gaw
+        self.buckets = check_buckets(kind, buckets)
+        if kind == "text2mel" and any(n > gaw.shape[0] or t > gaw.shape[1] for n, t in self.buckets):
+            raise ValueError("BucketedTrainStep: a bucket exceeds the guided-attention weights %s" % (tuple(gaw.shape),))
+        self.own_ddp = ddp is None
+        self.ddp = ddp if ddp is not None else DataParallelRanks(model=model, segmented=False)
+        self.defer_wgrad = defer_wgrad
+        self.batch_size = batch_size
+        self.steps = {}
+        self.replays = self.eager = self.captures = 0
+        self.capture_seconds = 0.0
+        self.pool_bytes = {}
+        self.last_bucket = None
+
+    def close(self):
+        """Drop every captured graph; a gradient arena made here is released from the model."""
+        for st in self.steps.values():
+            st.release()
+        self.steps = {}
+        if self.own_ddp:
+            self.ddp.close()
+
+    def _need(self, batch):
+        if self.kind == "text2mel":
+            mel, text, _ = batch
+            return (int(text.shape[-1]), int(mel.shape[-1]))
+        mel, lin = batch
+        if lin.shape[-1] != 4 * mel.shape[-1]:
+            raise ValueError("BucketedTrainStep: SSRN target has %d frames for %d mel frames (want 4x)" % (lin.shape[-1], mel.shape[-1]))
+        return (int(mel.shape[-1]),)
+
+    def _static(self, bucket, batch):
+        if self.kind == "text2mel":
+            N, T = bucket
+            mel, text, spk = batch
+            shapes = [(mel.shape[0], mel.shape[1], T), (text.shape[0], text.shape[1], N), tuple(spk.shape)]
+        else:
+            (T,) = bucket
+            mel, lin = batch
+            shapes = [(mel.shape[0], mel.shape[1], T), (lin.shape[0], lin.shape[1], 4 * T)]
+        return [torch.zeros(s, dtype=b.dtype, device=b.device) for s, b in zip(shapes, batch)]
+
+    def _capture(self, bucket, batch):
+        import time
+        dev = batch[0].device
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        lens = torch.tensor(bucket, dtype=torch.int32, device=dev)
+        static = self._static(bucket, batch)
+        for d, b in zip(static, batch):
+            _pad_into(d, b)
+        # the capture's warm-up iterations train: keep weights and optimizer state, and put them back (into the same tensors) afterwards
+        saved_w = [p.detach().clone() for p in self.model.parameters()]
+        saved_opt = {id(p): (st["exp_avg"].clone(), st["exp_avg_sq"].clone()) for p, st in self.opt.state.items() if "exp_avg" in st}
+        # the true step count: replays advance only the device counter, so the host's is stale once any graph has run
+        steps = int(self.opt._step_dev.item()) if self.opt._step_dev is not None else self.opt._steps
+        st = TrainStep(self.kind, self.model, self.opt, None, self.gaw, self.ddp, graph=True, defer_wgrad=self.defer_wgrad, lens=lens)
+        st.static = st.batch = static
+        st.prepare()
+        torch.cuda.synchronize()
+        with torch.no_grad():
+            for p, w in zip(self.model.parameters(), saved_w):
+                p.copy_(w)
+            for p, s in self.opt.state.items():
+                if "exp_avg" in s:
+                    m, v = saved_opt.get(id(p), (None, None))
+                    if m is None:
+                        s["exp_avg"].zero_()
+                        s["exp_avg_sq"].zero_()
+                    else:
+                        s["exp_avg"].copy_(m)
+                        s["exp_avg_sq"].copy_(v)
+        self.opt._steps = steps
+        if self.opt._step_dev is not None:
+            self.opt._step_dev.fill_(steps)
+        self.opt.refresh_resident_weights()          # (the copies above bumped the weights' versions: the planes are re-split in place)
+        torch.cuda.synchronize()
+        del saved_w, saved_opt
+        self.capture_seconds += time.perf_counter() - t0
+        self.captures += 1
+        pool = tuple(st.stepper.pool)
+        self.pool_bytes[bucket] = sum(4 * b.numel() if b.dtype != torch.int64 else 8 * b.numel() for b in static) + sum(
+            seg["total_size"] for seg in torch.cuda.memory_snapshot() if tuple(seg.get("segment_pool_id", ())) == pool)
+        st.lens_host = torch.empty(len(bucket), dtype=torch.int32).pin_memory()     # staging for the live lengths (see __call__)
+        st.lens_copied = None
+        self.steps[bucket] = st
+        return st
+
+    def __call__(self, *batch):
+        """One iteration on ``batch`` ((mel, text, spk) or (mel, lin), each at its own batch maxima); returns the loss terms as
+        ``TrainStep`` does."""
+        need = self._need(batch)
+        bucket = pick_bucket(self.buckets, need)
+        B = int(batch[0].shape[0])
+        st = self.steps.get(bucket) if bucket is not None else None
+        want_b = self.batch_size if self.batch_size is not None else (st.static[0].shape[0] if st is not None else B)
+        self.last_bucket = bucket
+        if bucket is None or B != want_b:
+            self.eager += 1
+            self.last_bucket = None
+            step = TrainStep(self.kind, self.model, self.opt, list(batch), self.gaw, self.ddp, graph=False)
+            out = step()
+            self.att = step.att
+            return out
+        if st is None:
+            st = self._capture(bucket, batch)
+        for d, b in zip(st.static, batch):
+            _pad_into(d, b)
+        if st.lens_copied is not None:
+            st.lens_copied.synchronize()          # the previous asynchronous copy out of the pinned buffer has run (long since, as a rule)
+        for j, v in enumerate(need):
+            st.lens_host[j] = v
+        st.lens.copy_(st.lens_host, non_blocking=True)
+        st.lens_copied = torch.cuda.Event()
+        st.lens_copied.record()
+        st.stepper.run()
+        self.replays += 1
+        self.att = st.att
+        return st.out
 
 
 # --------------------------------------------------------------------------------------------- WGAN-GP

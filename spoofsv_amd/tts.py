@@ -15,6 +15,8 @@ The ``nn.Conv1d`` / ``nn.LayerNorm`` / ``nn.Linear`` / ``nn.ConvTranspose1d`` ch
 containers only (they give the reference's initialisation order and key names); their stock
 ``forward`` is never called -- all compute goes through ``spoofsv_amd.ops`` into libssv_hip.so.
 """
+import contextlib
+
 import torch
 import torch.nn as nn
 
@@ -46,7 +48,7 @@ class highwayConv(nn.Module):
 
     def forward(self, inputs):
         return ops.highway_conv1d(inputs, self.conv.weight, self.conv.bias, self.ln1.weight, self.ln1.bias,
-                                  self.ln2.weight, self.ln2.bias, self.kernel_size, self.dilation, self.causal)
+                                  self.ln2.weight, self.ln2.bias, self.kernel_size, self.dilation, self.causal, _live(self))
 
 
 class highwayDilationIncrement(nn.Module):
@@ -61,8 +63,49 @@ class highwayDilationIncrement(nn.Module):
         return self.hc4(self.hc3(self.hc2(self.hc1(inputs))))
 
 
-def _cla(x, conv, ln, s=None, act=0):
-    return ops.pointwise_conv_ln_act(x, conv.weight, conv.bias, ln.weight, ln.bias, s, act)
+def _cla(x, conv, ln, s=None, act=0, live=None):
+    return ops.pointwise_conv_ln_act(x, conv.weight, conv.bias, ln.weight, ln.bias, s, act, live)
+
+
+def _live(module):
+    """The ``ops.Live`` that ``live_lengths`` handed to ``module`` (None outside a length-masked step)."""
+    return module.__dict__.get("_ssv_live")
+
+
+@contextlib.contextmanager
+def live_lengths(model, lens):
+    """Run ``model`` (melSyn or SSRN, training forward) on a batch padded to a bucket shape, with the batch's own maxima in the int32
+    device tensor ``lens``: (N_b, T_b) for melSyn, (T_b,) for SSRN.  Then the padded step computes what the unpadded batch would
+    (DESIGN §5): the attention leaves padded keys and frames out, the losses count the live region only, and every layer whose output
+    feeds a NON-CAUSAL convolution of kernel 3 keeps that output, and the gradient its backward receives, exactly 0 past its live length
+    (N_b in the text encoder; T_b, 2 T_b, 4 T_b in SSRN's stages).  The other layers need no mask: 1x1 convolutions, LayerNorms, gates
+    and the transposed convolution are column-local, and a causal convolution reads only earlier columns, so padded columns never reach a
+    live one and their gradients stay 0 from the masked losses down.  Only a plain attribute is set on the modules for the duration:
+    parameters, state_dict keys and forward signatures are untouched."""
+    if isinstance(model, melSyn):
+        te, n = model.text_encoder, ops.Live(lens, 0)
+        # conv2 and every k = 3 highway layer that feeds another k = 3 layer (hc2 feeds the 1x1 hc3: no mask)
+        plan = [(m, n) for m in (te, te.hci1.hc1, te.hci1.hc2, te.hci1.hc3, te.hci1.hc4, te.hci2.hc1, te.hci2.hc2, te.hci2.hc3,
+                                 te.hci2.hc4, te.hc1)]
+        plan.append((model, n))                         # the attention reads (N_b, T_b) from lens[0], lens[1]
+    elif isinstance(model, SSRN):
+        # conv1, hc1 (-> k = 3 layers), both transposed convolutions and the first highway layer after each, conv2 and hc3
+        plan = [(m, ops.Live(lens, 0, 1)) for m in (model, model.hc1)]
+        plan += [(m, ops.Live(lens, 0, 2)) for m in (model.ups1, model.ups1.hc1)]
+        plan += [(m, ops.Live(lens, 0, 4)) for m in (model.ups2, model.ups2.hc1, model.hc3)]
+    else:
+        raise TypeError("live_lengths: a melSyn or an SSRN, not %s" % type(model).__name__)
+    prev = [(m, m.__dict__.get("_ssv_live")) for m, _ in plan]
+    try:
+        for m, lv in plan:
+            m.__dict__["_ssv_live"] = lv
+        yield model
+    finally:
+        for m, lv in prev:
+            if lv is None:
+                m.__dict__.pop("_ssv_live", None)
+            else:
+                m.__dict__["_ssv_live"] = lv
 
 
 def _no_cut(name, x):
@@ -90,9 +133,10 @@ class textEncoder(nn.Module):
 
     def encode(self, inputs, cut=_no_cut):
         """The un-split (B, 2*hidden, N) output; K is the first half, V the second (:138-139)."""
+        lv = _live(self)
         x = self.textemb_layer(inputs)
         x = _cla(x, self.conv1, self.ln1, act=1)      # relu feeds conv2 (:130)
-        x = _cla(x, self.conv2, self.ln2)
+        x = _cla(x, self.conv2, self.ln2, live=lv)
         x = cut("text_c0", self.hci1.hc1(x))                     # (hci1 spelled out: its first layer closes the LAST gradient bucket)
         x = cut("text_c1", self.hci1.hc4(self.hci1.hc3(self.hci1.hc2(x))))
         x = cut("text_c2", self.hci2(x))
@@ -187,7 +231,7 @@ class melSyn(nn.Module):
                 kv = self.text_encoder.encode(textid, self._cut)
             Q = self.audio_encoder(melspec, spkemb, self._cut)
             cur.wait_stream(side)     # join; kv stays alive until backward, no record_stream (illegal under capture) needed
-            RQ, A = ops.attention_train(kv, Q)
+            RQ, A = ops.attention_train(kv, Q, _live(self))
             return self.audio_decoder(self._cut("dec_in", RQ)), A
 
         # ---- synthesis step (models/TTSModel.py:275-300) ---------------------------------------
@@ -240,7 +284,7 @@ class upsampling(nn.Module):
         self.hc2 = highwayConv(dimension=ssrn_dim, kernel_size=3, dilation=3)
 
     def forward(self, inputs):
-        x = ops.deconv1d_k2s2(inputs, self.deconv.weight, self.deconv.bias)
+        x = ops.deconv1d_k2s2(inputs, self.deconv.weight, self.deconv.bias, _live(self))
         return self.hc2(self.hc1(x))
 
 
@@ -268,10 +312,12 @@ class SSRN(nn.Module):
         self.ln6 = nn.LayerNorm(normalized_shape=output_bins)
 
     def forward(self, inputs):
-        x = _cla(inputs, self.conv1, self.ln1)
+        lv = _live(self)
+        l4 = ops.Live(lv.lens, lv.index, 4 * lv.mult) if lv is not None else None       # after the two upsamplings
+        x = _cla(inputs, self.conv1, self.ln1, live=lv)
         x = self.hc2(self.hc1(x))
         x = self.ups2(self.ups1(x))
-        x = self._cut("ssrn_mid", _cla(x, self.conv2, self.ln2))
+        x = self._cut("ssrn_mid", _cla(x, self.conv2, self.ln2, live=l4))
         x = self._cut("ssrn_tail", self.hc4(self.hc3(x)))
         x = _cla(x, self.conv3, self.ln3)             # no ReLU between ln3 and conv4 (:355)
         x = _cla(x, self.conv4, self.ln4, act=1)
