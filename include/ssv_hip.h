@@ -478,6 +478,34 @@ int ssv_attention_column(const float* kv, long kv_bs, const float* q, int64_t* p
 /* End of a step: Y[:, :, t] = y_cur (B,F), mel_cur = y_cur (the next step's input frame, synthesize.py:108-109), t += 1. */
 int ssv_synth_column_advance(const float* y_cur, float* Y, float* mel_cur, int* t_dev, int B, int F, int T, ssv_stream_t stream);
 
+/* ---- Wide column-incremental synthesis: many items per step (generate_test_utterances.py:98-139 walks the speakers one by one;
+ * here S speakers x U sentences are the items of ONE free run) ---------------------------------------------------------------
+ * Step activations are CHANNEL-MAJOR, (C, Bw): the B items contiguous, Bw = B rounded up to ssv_column_wide_tile() columns, the pad
+ * columns B .. Bw-1 zero (every entry below writes them as zeros).  A layer is one launch: a matrix product over the batch on the
+ * MFMA units in the mode of ssv_set_precision -- exact fp32 reads `w`, the split modes read the weight's resident planes `w_packed`
+ * (ssv_conv_pack_multi) and fail with -1 when they are NULL -- whose workgroups own all output rows of their columns and finish bias,
+ * LayerNorm and activation / gate in the epilogue.  split-fp16: the operand scale is that of the workgroup's own column tile.
+ * Codes: NULL pointers, non-positive sizes, B > Bw, U = 0 or B % U != 0, an output that is its own input: -1; a shape the tile cannot take
+ * (k != 3, C % 8 != 0 or C > 256 for the highway layer, Cout > 512, Bw not a multiple of the tile): -2.  All checked before any launch.
+ * ssv_column_highway_wide: models/TTSModel.py:28-47 (highwayConv.forward, causal, kernel size 3) for frame t = *t_dev of every item:
+ *   h = W0 x[t-2d] + W1 x[t-d] + W2 x[t] + bias (2C rows; a tap before frame 0 is zero), H1 | H2 = its halves,
+ *   out = sigmoid(LN1(H1)) * LN2(H2) + (1 - sigmoid(LN1(H1))) * x[t];  x[t] = cur (C, Bw) is filed as frame t of hist (Tmax, C, Bw),
+ *   the two earlier taps are read from there.  w (2C, C, 3) as nn.Conv1d keeps it. */
+int ssv_column_wide_tile(void);
+int ssv_column_highway_wide(const float* w, const void* w_packed, const float* bias, const float* g1, const float* b1, const float* g2,
+                            const float* b2, const float* cur, float* hist, int Tmax, const int* t_dev, int dilation, float* out,
+                            int B, int Bw, int C, int k, ssv_stream_t stream);
+/* y (Cout, Bw) = act(LN(W x + bias [+ s])) for x (Cin, Bw): the 1x1 links, models/TTSModel.py:128-131, :173-180, :218-231.  s (Cout, Bw) or
+ * NULL is the per-ITEM speaker term of the conditioned encoder (models/TTSModel.py:174,179).  act as ssv_channel_ln_act_fwd. */
+int ssv_column_pwln_wide(const float* x, const float* w, const void* w_packed, const float* bias, const float* s, const float* gamma,
+                         const float* beta, float* y, int B, int Bw, int Cin, int Cout, int act, ssv_stream_t stream);
+/* ssv_attention_column (models/TTSModel.py:281-295) with q (d, Bw) and rq (2d, Bw) = [V a ; q] in the wide layout; item b reads text
+ * b % U of kv (U, 2d, N) (U = B: a text per item).  pma (B) and a (B, N, a_T) as there. */
+int ssv_attention_column_wide(const float* kv, long kv_bs, int U, const float* q, int64_t* pma, float* a, int a_T, const int* t_dev,
+                              float* rq, int B, int Bw, int d, int N, ssv_stream_t stream);
+/* End of a step (synthesize.py:108-109): frame t of Y (T, F, Bw) = y_cur (F, Bw), mel_cur = y_cur, t += 1. */
+int ssv_synth_column_advance_wide(const float* y_cur, float* Y, float* mel_cur, int* t_dev, int Bw, int F, int T, ssv_stream_t stream);
+
 /* ---- Critic glue: what models/discriminator.py:24-41 does between its convolutions and LayerNorms ----------
  * Dropout(p = 0.05) (always active: the reference never calls disc.eval()), leaky-ReLU(0.05), AvgPool1d, and the reduction of
  * the gradient penalty (train/adversarial_wasserstein_gp.py:305-308).  Each is (piecewise) linear, hence differentiable to any

@@ -300,6 +300,9 @@ static size_t pack_bytes(int Cout, int Cin, int k) { return 2 * split_bytes(Cout
 static const float* packed_inv(const void* w_packed, int Cout, int Cin, int k, int transposed) {
   return w_packed ? (const float*)((const char*)w_packed + pack_bytes(Cout, Cin, k) - 256 + (transposed ? 128 : 0)) : nullptr;
 }
+// (for synth_wide.hip, which reads resident planes without going through conv_nn)
+size_t ssv_split_bytes(int rows, int K, int k) { return split_bytes(rows, K, k); }
+const float* ssv_packed_inv(const void* w_packed, int Cout, int Cin, int k, int transposed) { return packed_inv(w_packed, Cout, Cin, k, transposed); }
 extern "C" size_t ssv_conv1d_fwd_workspace(int Cin, int Cout, int k) { return 2 * split_bytes(Cout, Cin, k) + conv_aux_bytes(); }
 extern "C" int ssv_conv1d_fwd(const float* x, long x_bs, const float* x_amax, int x_namax, const float* w, const void* w_packed, const float* bias,
                               const float* bias_b, float* y, long y_bs, float* y_colstats,

@@ -158,6 +158,9 @@ int ssv_launch_absmax(const float* x, long x_bs, int B, long n, float* out, int 
 int ssv_nt_bf3_tiles(int KT, int M, int Nc);
 void ssv_nt_bf3_tile(int KT, int M, int Nc, int* wm, int* ntc);
 int ssv_nt_bf3_wg_per_cu(int KT, int wm, int ntc);        // co-resident workgroups per CU of that instantiation (its register count)
+// layout of a weight's resident planes (api.hip): bytes of ONE plane (the lo plane follows the hi plane), and where 2^-ea is kept (split-fp16)
+size_t ssv_split_bytes(int rows, int K, int k);
+const float* ssv_packed_inv(const void* w_packed, int Cout, int Cin, int k, int transposed);
 int ssv_precision();      // 0 = exact fp32 MFMA, 1 = split-bf16 MFMA, 2 = split-fp16 MFMA with power-of-two operand scales (default)
 // The three tuning knobs that remain (per-shape overrides for in-step sweeps: SSV_NNB_FORCE="kt:M:N=wm,nt;...", SSV_NT_FORCE="M:Nc:k=Z;...",
 // SSV_LN_GROUPS for tools/bench_ln.py): read from the environment ONCE at first use -- a launch must not cost getenv() scans -- and

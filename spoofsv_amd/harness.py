@@ -299,11 +299,14 @@ def _adam(params, cfg, fused=True):
     return torch.optim.Adam(params, a["ALPHA"], (a["BETA_1"], a["BETA_2"]), a["EPSILON"])
 
 
-def _free_run(model, text_id, spk_emb, frames, freq_bins, graph=False, incremental=False):
+def _free_run(model, text_id, spk_emb, frames, freq_bins, graph=False, incremental=False, wide=False, shared_texts=None):
     """The reference's synthesis loop (synthesize.py:103-109, ordinary.py:59-65).  ``graph=True`` runs the same loop as
     a replayed hipGraph of one fixed-shape step (spoofsv_amd/synth.py; config key SYNTH_GRAPH): 1.5x faster at batch 1,
     same values up to the arithmetic mode of the first few frames (short prefixes run the exact-fp32 kernels step by step)."""
     resident.ensure(model, ops._stream())       # frozen weights: split once, not once per conv call (~30 launches per step)
+    if wide:              # many items per run: every layer of the column step one MFMA product over the batch (synth.WideSynthesizer);
+        from . import synth       # shared_texts = U: text_id holds U texts, item b of spk_emb speaks text b % U
+        return synth.free_run_wide(model, text_id, spk_emb, frames, shared_texts=shared_texts)
     if incremental:       # config key SYNTH_INCREMENTAL (default on in synthesize / generate_test_utterances): one new column
         from . import synth       # per step instead of the whole prefix (spoofsv_amd/synth.py, IncrementalSynthesizer)
         return synth.free_run_incremental(model, text_id, spk_emb, frames)
@@ -730,14 +733,34 @@ def synthesize(pattern, cfg, spec_dir, current_time=None, texts=None, spk_emb=No
     return outs
 
 
-def generate_test_utterances(cfg, current_time, eval_utt_num=20, speakers=None, texts=None, max_frames=None):
+def plan_utterance_groups(n_speakers, n_texts, speakers_per_batch):
+    """How ``generate_test_utterances`` batches its free runs: a list of groups, each the list of (speaker index, sentence index) of
+    the group's items in item order.  Speakers are taken ``speakers_per_batch`` at a time in their given order, the last group may be
+    smaller (it runs on a synthesizer of its own size; nothing is padded); inside a group item ``b`` is speaker ``b // n_texts`` of
+    the group speaking sentence ``b % n_texts``.  Read group after group, item after item, this is the order of today's per-speaker loop."""
+    S = int(speakers_per_batch)
+    if S < 1 or n_speakers < 0 or n_texts < 1:
+        raise ValueError("plan_utterance_groups: speakers_per_batch and the number of texts must be at least 1")
+    return [[(s, u) for s in range(s0, min(s0 + S, n_speakers)) for u in range(n_texts)] for s0 in range(0, n_speakers, S)]
+
+
+def generate_test_utterances(cfg, current_time, eval_utt_num=20, speakers=None, texts=None, max_frames=None, speakers_per_batch=None):
     """generate_test_utterances.py:56-139: for every speaker, synthesize the first ``eval_utt_num`` sentences of TTS_TEXTS as
     ONE batch (texts zero-padded to a common length, :67-72; the speaker code repeated, :105) -- Text2Mel free run for
     MAX_FRAME_NUM further steps (:108-116), SSRN (:120), then per utterance Griffin-Lim(64), de-emphasis, trim(30 dB), clip to
     9 s, peak 0.75 and ``s<id>/s<id>_<nnn>.wav`` (:128-139).  Here the vocoder runs once per speaker on the whole batch
     (spoofsv_amd.vocoder); only trim / clip / write stay per utterance on the host.  The Kaldi / GE2E / ASVspoof trial-list
     bookkeeping of :141-260 is not reproduced.  ``speakers``: {name: (SPK_EMB_DIM,) array}; default: the .npy files of
-    SPK_EMB_DIR.  Returns {speaker: [wav paths]}."""
+    SPK_EMB_DIR.  Returns {speaker: [wav paths]}.
+
+    ``speakers_per_batch`` (config key SYNTH_SPEAKERS_PER_BATCH, default 1 = the loop above, unchanged): with S > 1 the speakers are
+    taken S at a time and ONE free run synthesizes S x ``eval_utt_num`` items on the wide column step (``synth.WideSynthesizer``), the
+    texts encoded once and shared (``plan_utterance_groups``); SSRN and the vocoder then run over that result one speaker's
+    sentences at a time, as today, with the same trim / clip / peak / file names.  A last, smaller group runs on a synthesizer of
+    its own size.  A frame of the wide step costs the same 1.1-1.3 ms for 20 items and for 2,160 (the per-speaker
+    loop costs 0.27 ms per frame and speaker), so small groups LOSE: measured 0.24x at S = 1, 0.90x at S = 4, 3.5x at S = 16, 11.7x at
+    S = 54, 23x at S = 108.  Use S >= 16 -- the smallest measured value at which the grouped run is not slower -- and as many speakers as
+    the device memory takes (``synth.wide_synth_bytes``: 5.4 MB per item at 326 frames, 11.3 GiB for 108 speakers)."""
     from scipy.io import wavfile
     from .vocoder import Vocoder, trim_silence
     dev = _device()
@@ -766,11 +789,30 @@ def generate_test_utterances(cfg, current_time, eval_utt_num=20, speakers=None, 
     save_dir = os.path.join(cfg["SRC_ROOT_DIR"], "test", str(current_time), "spoof_data")
     frames = (max_frames or cfg["MAX_FRAME_NUM"]) + 1                   # first frame + MAX_FRAME_NUM further steps (:110-116)
     sr, out = cfg["SAMPLING_RATE"], {}
+    if speakers_per_batch is None:
+        speakers_per_batch = cfg.get("SYNTH_SPEAKERS_PER_BATCH", 1)
+    names, U = list(speakers), len(ids)
+
+    def code(spk):
+        return torch.as_tensor(np.asarray(speakers[spk], dtype=np.float32), device=dev).view(1, -1, 1).expand(U, -1, -1)
+
+    def mels():
+        """(speaker, Y (U, F, frames)) in the speakers' order"""
+        if int(speakers_per_batch) <= 1:
+            for spk in names:
+                Y, _ = _free_run(m1, text_id, code(spk).contiguous(), frames, cfg["COARSE_MELSPEC"]["FREQ_BINS"], graph=cfg.get("SYNTH_GRAPH", False),
+                                 incremental=cfg.get("SYNTH_INCREMENTAL", True))
+                yield spk, Y
+            return
+        for group in plan_utterance_groups(len(names), U, speakers_per_batch):
+            members = [names[s] for s, u in group if u == 0]
+            e = torch.cat([code(spk) for spk in members], dim=0).contiguous()
+            Yg, _ = _free_run(m1, text_id, e, frames, cfg["COARSE_MELSPEC"]["FREQ_BINS"], wide=True, shared_texts=U)
+            for i, spk in enumerate(members):
+                yield spk, Yg[i * U:(i + 1) * U].contiguous()
+
     with torch.no_grad():
-        for spk, emb in speakers.items():
-            e = torch.as_tensor(np.asarray(emb, dtype=np.float32), device=dev).view(1, -1, 1).expand(len(ids), -1, -1).contiguous()
-            Y, _ = _free_run(m1, text_id, e, frames, cfg["COARSE_MELSPEC"]["FREQ_BINS"], graph=cfg.get("SYNTH_GRAPH", False),
-                             incremental=cfg.get("SYNTH_INCREMENTAL", True))
+        for spk, Y in mels():
             resident.ensure(m2, ops._stream())
             lin = m2(Y).contiguous()
             wav = voc.spectrogram2wav(lin, cfg, n_iter=cfg.get("GRIFFIN_LIM_ITERS", 64), graph=cfg.get("SYNTH_GRAPH", False),

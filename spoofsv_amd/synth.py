@@ -268,3 +268,188 @@ def free_run_incremental(model, text_id, spk_emb, frames):
     key = (id(model), text_id.shape[0], text_id.shape[2], frames)
     g = _cached(_ICACHE, key, model, lambda: IncrementalSynthesizer(model, text_id.shape[0], text_id.shape[2], frames, text_id.device))
     return g.run(text_id, spk_emb)
+
+
+# ------------------------------------------------------------------------------------------------ wide column-incremental synthesis
+def _wide_tile():
+    from . import _lib
+    return int(_lib.lib().ssv_column_wide_tile())
+
+
+def _wide_buffers(batch, text_len, frames, hidden, freq_bins, shared_texts=None, n_highway=16, tile=32):
+    """(name, shape, bytes per element) of every device buffer a ``WideSynthesizer`` of this shape allocates."""
+    B, N, T, d, F = batch, text_len, frames, hidden, freq_bins
+    Bw = -(-B // tile) * tile
+    U = B if shared_texts is None else shared_texts
+    bufs = [("kv", (U, 2 * d, N), 4), ("mel_cur", (F, Bw), 4), ("Yw", (T, F, Bw), 4), ("A", (B, N, T), 4), ("pma", (B,), 8), ("t", (1,), 4),
+            ("s1", (d, Bw), 4), ("s2", (d, Bw), 4), ("a", (d, Bw), 4), ("b", (d, Bw), 4), ("rq", (2 * d, Bw), 4), ("y_cur", (F, Bw), 4)]
+    bufs += [("hist%d" % i, (T, d, Bw), 4) for i in range(n_highway)]
+    return bufs
+
+
+def wide_synth_bytes(batch, text_len, frames, hidden=256, freq_bins=80, shared_texts=None, n_highway=16, tile=32):
+    """Device bytes a ``WideSynthesizer(model, batch, text_len, frames, ...)`` holds (its own buffers; the model and its resident weight
+    planes are not counted).  Nearly all of it is the input history of the ``n_highway`` causal kernel-3 layers, kept whole:
+    ``frames * hidden * Bw`` floats each with ``Bw`` = ``batch`` rounded up to the column tile (32)."""
+    total = 0
+    for _, shape, size in _wide_buffers(batch, text_len, frames, hidden, freq_bins, shared_texts, n_highway, tile):
+        n = size
+        for s in shape:
+            n *= s
+        total += n
+    return total
+
+
+class WideSynthesizer:
+    """``IncrementalSynthesizer`` for LARGE batches: the same column-incremental step with every layer as ONE matrix product over the
+    batch on the MFMA units (include/ssv_hip.h, "Wide column-incremental synthesis"; csrc/synth_wide.hip), 27 launches per frame.
+    Step activations are (C, Bw) with the items contiguous.  The weights are read from the model's resident pre-split planes
+    (``resident.ensure``), re-split at the start of every ``run``: no second copy, no tap-major repack.
+
+    ``shared_texts=U``: ``text_id`` is (U, 1, N), ``spk_emb`` (B, spkemb_dim, 1) with ``B % U == 0`` and item ``b`` speaks text ``b % U`` --
+    S speakers x U sentences need one text-encoder call and one K | V.  Same contract as ``IncrementalSynthesizer`` otherwise (eval mode,
+    ``run(text_id, spk_emb) -> (Y (B, F, frames), A (B, N, frames))``).  In the split-fp16 mode an item's operand scale is that of its
+    32-column tile, so its values depend on its neighbours to rounding (not at all in the fp32 mode)."""
+
+    def __init__(self, model, batch, text_len, frames, device, shared_texts=None):
+        if model.training:
+            raise RuntimeError("WideSynthesizer needs the model in eval mode")
+        import ctypes
+        from . import _lib, resident
+        self._lib, self._vp, self._resident = _lib, ctypes.c_void_p, resident
+        U = shared_texts
+        if U is not None and (U <= 0 or batch % U != 0):
+            raise RuntimeError("WideSynthesizer: %d items do not divide into %r shared texts" % (batch, U))
+        self.model, self.B, self.N, self.T, self.dev, self.U = model, batch, text_len, frames, device, U
+        self.addresses = _addresses(model)
+        enc, dec = model.audio_encoder, model.audio_decoder
+        self.d, self.F = model.hidden_dim, dec.conv5.out_channels
+        self.enc_hw = [enc.hci1.hc1, enc.hci1.hc2, enc.hci1.hc3, enc.hci1.hc4, enc.hci2.hc1, enc.hci2.hc2, enc.hci2.hc3, enc.hci2.hc4,
+                       enc.hc1, enc.hc2]
+        self.dec_hw = [dec.hci.hc1, dec.hci.hc2, dec.hci.hc3, dec.hci.hc4, dec.hc1, dec.hc2]
+        for hc in self.enc_hw + self.dec_hw:
+            if not (hc.causal and hc.kernel_size == 3 and hc.dimension == self.d):
+                raise RuntimeError("WideSynthesizer: unexpected highwayConv configuration")
+        self.tile = _wide_tile()
+        self.Bw = -(-batch // self.tile) * self.tile
+        bufs = _wide_buffers(batch, text_len, frames, self.d, self.F, U, len(self.enc_hw + self.dec_hw), self.tile)
+        need = wide_synth_bytes(batch, text_len, frames, self.d, self.F, U, len(self.enc_hw + self.dec_hw), self.tile)
+        if torch.device(device).type == "cuda":
+            free = torch.cuda.mem_get_info(device)[0] + torch.cuda.memory_reserved(device) - torch.cuda.memory_allocated(device)
+            if need > free:
+                raise RuntimeError("WideSynthesizer(batch=%d, text_len=%d, frames=%d) needs %d bytes of device memory (%.1f GB), %d are free: "
+                                   "run fewer items per batch" % (batch, text_len, frames, need, need / 2.0 ** 30, free))
+        self.nbytes = need
+        self.hist = []
+        for name, shape, size in bufs:
+            t = torch.zeros(shape, dtype=torch.int64 if size == 8 else (torch.int32 if name == "t" else torch.float32), device=device)
+            if name.startswith("hist"):
+                self.hist.append(t)
+            else:
+                setattr(self, name, t)
+        self.graph, self._key = None, None
+
+    def _p(self, t):
+        return None if t is None else self._vp(t.data_ptr())
+
+    def _weights(self):
+        enc, dec = self.model.audio_encoder, self.model.audio_decoder
+        return [c.weight for c in (enc.conv1, enc.conv2, enc.conv3, dec.conv1, dec.conv2, dec.conv3, dec.conv4, dec.conv5)] + \
+               [hc.conv.weight for hc in self.enc_hw + self.dec_hw]
+
+    def _planes(self, w):
+        if self._lib.precision() == 0:
+            return None
+        pl = self._resident.lookup(w)
+        if pl is None:
+            raise RuntimeError("WideSynthesizer: a weight has no resident planes (resident.ensure did not cover it)")
+        return pl
+
+    def _link(self, conv, ln, x, y, act=0, s=None):
+        Cout, Cin, _ = conv.weight.shape
+        self._lib.call("ssv_column_pwln_wide", self._p(x), self._p(conv.weight), self._planes(conv.weight), self._p(conv.bias), self._p(s),
+                       self._p(ln.weight), self._p(ln.bias), self._p(y), self.B, self.Bw, Cin, Cout, act, ops._stream())
+
+    def _highway(self, hc, hist, cur, out):
+        w = hc.conv.weight
+        self._lib.call("ssv_column_highway_wide", self._p(w), self._planes(w), self._p(hc.conv.bias), self._p(hc.ln1.weight), self._p(hc.ln1.bias),
+                       self._p(hc.ln2.weight), self._p(hc.ln2.bias), self._p(cur), self._p(hist), self.T, self._p(self.t), hc.dilation,
+                       self._p(out), self.B, self.Bw, self.d, 3, ops._stream())
+
+    def _step(self):
+        enc, dec, d = self.model.audio_encoder, self.model.audio_decoder, self.d
+        a, b = self.a, self.b
+        cond = enc.condition
+        self._link(enc.conv1, enc.ln1, self.mel_cur, a, act=1, s=self.s1 if cond else None)
+        self._link(enc.conv2, enc.ln2, a, b, act=1)
+        self._link(enc.conv3, enc.ln3, b, a, s=self.s2 if cond else None)
+        cur, nxt, h = a, b, 0
+        for hc in self.enc_hw:
+            self._highway(hc, self.hist[h], cur, nxt)
+            cur, nxt, h = nxt, cur, h + 1
+        self._lib.call("ssv_attention_column_wide", self._p(self.kv), self.kv.stride(0), self.kv.shape[0], self._p(cur), self._p(self.pma),
+                       self._p(self.A), self.T, self._p(self.t), self._p(self.rq), self.B, self.Bw, d, self.N, ops._stream())
+        self._link(dec.conv1, dec.ln1, self.rq, a)
+        cur, nxt = a, b
+        for hc in self.dec_hw:
+            self._highway(hc, self.hist[h], cur, nxt)
+            cur, nxt, h = nxt, cur, h + 1
+        self._link(dec.conv2, dec.ln2, cur, nxt, act=1)
+        self._link(dec.conv3, dec.ln3, nxt, cur, act=1)
+        self._link(dec.conv4, dec.ln4, cur, nxt, act=1)
+        self._link(dec.conv5, dec.ln5, nxt, self.y_cur, act=2)
+        self._lib.call("ssv_synth_column_advance_wide", self._p(self.y_cur), self._p(self.Yw), self._p(self.mel_cur), self._p(self.t),
+                       self.Bw, self.F, self.T, ops._stream())
+
+    def _capture(self):
+        s = torch.cuda.Stream()
+        s.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(s), torch.no_grad():
+            self._step()
+        torch.cuda.current_stream().wait_stream(s)
+        torch.cuda.synchronize()
+        self.graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(self.graph), torch.no_grad():
+            self._step()
+
+    @torch.no_grad()
+    def run(self, text_id, spk_emb):
+        B, N, T, U = self.B, self.N, self.T, self.U
+        nt = B if U is None else U
+        if tuple(text_id.shape) != (nt, 1, N):
+            raise RuntimeError("WideSynthesizer was built for text ids of shape %s, got %s" % ((nt, 1, N), tuple(text_id.shape)))
+        enc = self.model.audio_encoder
+        # FusedAdam writes weights through raw pointers, so no version counter tells whether the planes are current: re-split them
+        # (one launch per plane set and run, against 27 launches per frame)
+        self._resident.invalidate(list(self.model.parameters()))
+        self._resident.ensure(self.model, ops._stream())
+        mode = self._lib.precision()
+        key = (mode,) + tuple(None if mode == 0 else self._resident.lookup(w).value for w in self._weights())
+        if key != self._key:                     # the captured step holds the plane addresses and the arithmetic mode's kernels
+            self.graph, self._key = None, key
+        self.kv.copy_(self.model.text_encoder.encode(text_id))
+        if enc.condition:
+            spk = spk_emb.to(self.dev).float()
+            if tuple(spk.shape[:1]) != (B,):
+                raise RuntimeError("WideSynthesizer was built for %d items, got %d speaker codes" % (B, spk.shape[0]))
+            self.s1[:, :B].copy_(ops.conv1d(spk, enc.fc1.weight.unsqueeze(-1), enc.fc1.bias).reshape(B, self.d).t())
+            self.s2[:, :B].copy_(ops.conv1d(spk, enc.fc2.weight.unsqueeze(-1), enc.fc2.bias).reshape(B, self.d).t())
+        self.mel_cur.zero_(); self.pma.zero_(); self.t.zero_(); self.A.zero_(); self.Yw.zero_()
+        if self.graph is None:
+            self._capture()                      # (its two steps ran on frame 0 and 1 of the buffers: start again)
+            self.mel_cur.zero_(); self.pma.zero_(); self.t.zero_(); self.A.zero_(); self.Yw.zero_()
+        for _ in range(T):
+            self.graph.replay()
+        return self.Yw[:, :, :B].permute(2, 1, 0).contiguous(), self.A.clone()
+
+
+_WCACHE = {}
+
+
+def free_run_wide(model, text_id, spk_emb, frames, shared_texts=None):
+    """Drop-in for ``free_run_incremental`` on the wide step (cached per model / batch / text length / frames / shared texts).  With
+    ``shared_texts=U``: ``text_id`` (U, 1, N), ``spk_emb`` (B, spkemb_dim, 1), item ``b`` speaks text ``b % U``."""
+    B = text_id.shape[0] if shared_texts is None else spk_emb.shape[0]
+    key = (id(model), B, text_id.shape[2], frames, shared_texts)
+    g = _cached(_WCACHE, key, model, lambda: WideSynthesizer(model, B, text_id.shape[2], frames, text_id.device, shared_texts))
+    return g.run(text_id, spk_emb)

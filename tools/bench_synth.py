@@ -10,6 +10,49 @@ dev = "cuda:0"
 torch.manual_seed(1234)
 m = melSyn(34, True, 200); m.apply(train.init_weights); m = m.to(dev).eval()
 s = SSRN(80, 513, 256); s.apply(train.init_weights); s = s.to(dev).eval()
+
+def wide_arms(speaker_counts, reps=5):
+    """--wide: S speakers x 20 sentences (N = 43, 326 frames) as (a) the per-speaker loop of generate_test_utterances -- free_run_incremental
+    at B = 20, S times: S x the median of one speaker's run, the runs being identical --, (b) free_run_incremental at B = 20 S in one run,
+    (c) free_run_wide with the 20 texts shared.  Warm-up (capture) excluded, median of `reps` runs with min / max."""
+    from spoofsv_amd import synth
+    U, N, frames = 20, 43, 326
+    text = torch.randint(2, 33, (U, 1, N), device=dev); text[:, :, -1] = 1
+
+    def timed(fn):
+        fn(); torch.cuda.synchronize()                      # capture / warm-up
+        ts = []
+        for _ in range(reps):
+            t0 = time.perf_counter(); fn(); torch.cuda.synchronize(); ts.append(time.perf_counter() - t0)
+        ts.sort()
+        return ts[len(ts) // 2], ts[0], ts[-1]
+
+    with torch.no_grad():
+        one = (0.04 + 0.05 * torch.rand(1, 200, 1, device=dev)).expand(U, -1, -1).contiguous()
+        loop1 = timed(lambda: synth.free_run_incremental(m, text, one, frames))
+        print("one speaker, free_run_incremental B=20: %.1f ms (min %.1f max %.1f), %.3f ms/frame" %
+              (loop1[0] * 1e3, loop1[1] * 1e3, loop1[2] * 1e3, loop1[0] / frames * 1e3), flush=True)
+        print("| S | items | per-speaker loop ms/frame | big batch ms/frame (min-max) | wide ms/frame (min-max) | wide item-frames/s | wide / loop |", flush=True)
+        for S in speaker_counts:
+            B = S * U
+            spk = (0.04 + 0.05 * torch.rand(S, 200, 1, device=dev)).repeat_interleave(U, dim=0).contiguous()
+            big = timed(lambda: synth.free_run_incremental(m, text.repeat(S, 1, 1), spk, frames))
+            synth._ICACHE.clear()                            # its (B, T, C) histories: 5.3 MB per item
+            wide = timed(lambda: synth.free_run_wide(m, text, spk, frames, shared_texts=U))
+            synth._WCACHE.clear()
+            torch.cuda.empty_cache()
+            f = 1e3 / frames
+            print("| %d | %d | %.3f | %.3f (%.3f-%.3f) | %.3f (%.3f-%.3f) | %.3g | %.2fx |" %
+                  (S, B, S * loop1[0] * f, big[0] * f, big[1] * f, big[2] * f, wide[0] * f, wide[1] * f, wide[2] * f,
+                   B * frames / wide[0], S * loop1[0] / wide[0]), flush=True)
+
+
+if "--wide" in sys.argv:
+    i = sys.argv.index("--wide")
+    counts = [int(v) for v in sys.argv[i + 1].split(",")] if len(sys.argv) > i + 1 else [1, 4, 16, 54, 108]
+    wide_arms(counts)
+    sys.exit(0)
+
 for B, N in ((1, 43), (8, 43), (32, 186)):
     text = torch.randint(2, 33, (B, 1, N), device=dev); text[:, :, -1] = 1
     spk = 0.04 + 0.05 * torch.rand(B, 200, 1, device=dev)
