@@ -430,6 +430,38 @@ int ssv_preemphasis(const float* x, float* y, float a, int B, int n, ssv_stream_
 int ssv_exp_affine(const float* x, float* y, float a, float b, long n, ssv_stream_t stream);
 int ssv_log_norm(const float* x, float* y, float ref_db, float max_db, long n, ssv_stream_t stream);
 
+/* ---- Speaker-verification front end: waveform -> GE2E features (additions; ABI version unchanged) ---------------------------
+ * Replaces GE2E/data_preprocess.py:45-60 (`librosa.core.load(path, sr)`, `librosa.effects.trim(utter, 30)`, `librosa.core.stft`,
+ * `np.abs(S)**2`, `np.dot(mel_basis, S)`, `np.log10(. + 1e-6)`, `S[:, :tisv_frame]` / `S[:, -tisv_frame:]`) for ragged batches:
+ * waveforms are (B, n_max) float32 rows, each with a live length in a DEVICE int array, so nothing between the vocoder's output and
+ * the embedder's input is read on the host and every shape is static.  The DFT between ssv_tisv_frames and ssv_power_mel_log is an
+ * ssv_conv1d_fwd call (k = 1) with a (2F, n_fft, 1) basis whose window (win_length <= n_fft, centred, zero-padded) the host builds.
+ * Codes: NULL pointers, non-positive sizes, hop > n_fft: -1; a ratio or size beyond the kernels' LDS tiles: -2. */
+/* resampy.resample(x, sr_orig, sr_new, filter='kaiser_best') as librosa.load applies it (:45), ratio up / down in lowest terms:
+ * y[b][t] = sum_j bank[(t * down) % up][j] * x[b][(t * down) / up - left + j] (x = 0 outside [0, n_in[b])), fp32, j ascending;
+ * bank (up, taps): the windowed-sinc table with resampy's linear interpolation and min(1, ratio) stretch folded in by the host.
+ * int(n_in * ratio) samples are computed, n_out[b] = ceil(n_in * ratio) (librosa's fix_length), zeros up to m_max >= ceil(n_max * ratio).
+ * up == down: a copy (bank may be NULL).  -2 when up * taps > 2^20 or a workgroup's input span exceeds 8192 samples. */
+int ssv_resample_sinc(const float* x, const int* n_in, const float* bank, float* y, int* n_out, int B, int n_max, int m_max,
+                      int up, int down, int taps, int left, ssv_stream_t stream);
+/* librosa.effects.trim(y, top_db) of librosa 0.7.0 (:46): centred frames of frame_length every hop (reflect padding; zero padding for a
+ * row no longer than frame_length / 2), mean square per frame in fp32, dB against the row's loudest frame;
+ * bounds[b] = (start, end) = (first frame above -top_db) * hop, min(n_in[b], (last such frame + 1) * hop); an empty row gives (0, 0).
+ * The loudest frame always passes, so a row of exact zeros keeps its whole length, as librosa's 1e-10 floor has it. */
+int ssv_trim_bounds(const float* y, const int* n_in, int* bounds, int B, int n_max, float top_db, int frame_length, int hop,
+                    ssv_stream_t stream);
+/* The centred, reflect-padded frames of librosa.stft(seg, n_fft, hop) that :55-60 keep, seg = y[b][start:end] from bounds (B, 2):
+ * fr (2B, n_fft, tisv_frame): item 2b the first tisv_frame frames, item 2b + 1 the last; valid[b] = (end - start) > min_len (:25, :48),
+ * frames of an invalid row are zeros.  min_len >= max(n_fft / 2, tisv_frame * hop). */
+int ssv_tisv_frames(const float* y, const int* bounds, float* fr, int* valid, int B, int n_max, int n_fft, int hop, int tisv_frame,
+                    int min_len, ssv_stream_t stream);
+/* out (R, T, nmels) = log10(mel (nmels, F) . |spec|^2 + eps), spec (R, 2F, T) as above (:50-52); plain fp32, f ascending; frames-major,
+ * as SpeechEmbedder.forward takes them.  F <= 1024. */
+int ssv_power_mel_log(const float* spec, const float* mel, float* out, int R, int F, int T, int nmels, float eps, ssv_stream_t stream);
+/* generate_test_utterances.py:135-139 after the trim, on the device: out (B, clip) = y[b][start : start + len] / max(that segment) * peak,
+ * len = min(end - start, clip), zeros after; n_out[b] = len.  The maximum, not the absolute maximum, as the reference has it. */
+int ssv_segment_peak(const float* y, const int* bounds, float* out, int* n_out, int B, int n_max, int clip, float peak, ssv_stream_t stream);
+
 /* ---- Second order, for the critics' gradient penalty ------------------------------------------
  * train/adversarial_wasserstein_gp.py:300-308 differentiates the critic's input gradient
  * (`autograd.grad(..., create_graph=True)` then `loss.backward()`), so the LayerNorm / highway-gate BACKWARD kernels need

@@ -2,6 +2,8 @@
 ``GE2E/data_load.py`` (preprocessed TI-SV data), ``GE2E/train_speech_embedder.py`` (``train``, ``test``,
 ``test_nospoof``: EER and spoof rate).  The embedder and the loss run in libssv_hip.so (``spoofsv_amd.ge2e``); data
 loading, the enrollment/verification bookkeeping and the threshold sweep are host logic, kept as the reference has them.
+``preprocess_tisv`` is ``GE2E/data_preprocess.py`` with its librosa pass on the device (``spoofsv_amd.sv_frontend``), and
+``spoof_evaluation`` the in-memory form of ``test`` for features that never touched a disk.
 
 Configuration is a plain dict with the fields of ``GE2E/config/config.yaml`` (``default_config()``), instead of the
 reference's module-global ``hparam`` object.
@@ -21,7 +23,8 @@ def default_config():
     """GE2E/config/config.yaml as shipped."""
     return {
         "training": False, "device": "cuda", "save_simmat_dir": "./simmat",
-        "data": {"train_path": "./train_tisv", "test_path": "./test_tisv", "nmels": 40, "tisv_frame": 120},
+        "data": {"train_path": "./train_tisv", "test_path": "./test_tisv", "sr": 16000, "nfft": 512, "window": 0.025,
+                 "hop": 0.01, "nmels": 40, "tisv_frame": 120},
         "model": {"hidden": 768, "num_layer": 3, "proj": 256, "model_path": None},
         "train": {"N": 6, "M": 50, "num_workers": 0, "lr": 0.01, "epochs": 950, "log_interval": 5, "log_file": None,
                   "checkpoint_interval": 120, "checkpoint_dir": "./speech_id_checkpoint", "restore": False},
@@ -207,3 +210,107 @@ def spoof_rate_at(cfg, thres, eval_num):
         idx = torch.arange(N)
         rates.append(float(mat[idx, -2 * eval_num:, idx].float().sum() / float(2 * eval_num) / N))
     return sum(rates) / len(rates)
+
+
+def read_wav(path):
+    """(rate, mono float32 waveform) of a PCM or float wav file, as ``harness.extract_features`` decodes them."""
+    from scipy.io import wavfile
+    sr, y = wavfile.read(path)
+    if y.ndim > 1:
+        y = y.mean(axis=1)                                       # librosa.load(mono=True)
+    if y.dtype.kind in "iu":
+        y = y.astype(np.float32) / float(1 << (8 * y.dtype.itemsize - 1))
+    return int(sr), np.ascontiguousarray(y, dtype=np.float32)
+
+
+def pad_batch(wavs, device):
+    """List of 1-D float waveforms -> ((B, n_max) float32, (B,) int32 lengths) on ``device``."""
+    n_max = max(1, max(len(w) for w in wavs))
+    y = np.zeros((len(wavs), n_max), dtype=np.float32)
+    for i, w in enumerate(wavs):
+        y[i, :len(w)] = w
+    return torch.from_numpy(y).to(device), torch.tensor([len(w) for w in wavs], dtype=torch.int32, device=device)
+
+
+def _fill_slices(specs, want):
+    """data_preprocess.py:69-74 / :76-81: a test speaker short of ``want`` utterances is filled with two random earlier slices per
+    missing one (``np.random.randint`` below HALF the number of slices, in the reference's call order)."""
+    have = len(specs)
+    if 2 * want - have > 0:
+        for _ in range(want - have // 2):
+            loc1 = np.random.randint(0, have // 2)
+            loc2 = np.random.randint(0, have // 2)
+            specs.extend([specs[loc1], specs[loc2]])
+
+
+def preprocess_tisv(cfg, speakers, train_spk_num, enroll_num, eval_num, front_end=None):
+    """data_preprocess.save_spectrogram_tisv (:15-93) with the librosa pass on the device.  ``speakers``: ordered {name: [wav paths]}
+    (the reference walks ``os.listdir`` order, which is not reproducible; the caller gives the order).  One device batch per speaker
+    and sample rate.  Training speakers (the first ``train_spk_num``) keep their first 100 files in the caller's order; a test speaker's
+    files are SORTED by base name without the extension, as :40 sorts them, and position k in that order decides the split: the first
+    ``enroll_num`` files are enrolment, the rest evaluation, each side filled up by random duplication (``np.random``); "Too short!!" utterances are
+    dropped.  Writes ``speaker<N>.npy`` as (slices, nmels, frames) under cfg["data"]["train_path"] / ["test_path"] and returns the
+    list of written paths.  As at the reference's ``__main__`` (:102), pass ``enroll_num`` = enrolment + evaluation utterances there
+    if the genuine evaluation utterances are to sit in the first block.
+    ``front_end(wavs, orig_sr) -> ((B, 2, tisv_frame, nmels) array, (B,) bool)`` replaces the device pass (tests inject a CPU restatement)."""
+    d = cfg["data"]
+    os.makedirs(d["train_path"], exist_ok=True)
+    os.makedirs(d["test_path"], exist_ok=True)
+    if front_end is None:
+        from .sv_frontend import TisvFrontEnd
+        fe = TisvFrontEnd.from_config(cfg)
+
+        def front_end(wavs, orig_sr):
+            f, v = fe(*pad_batch(wavs, fe.device), orig_sr)
+            return f.cpu().numpy(), v.cpu().numpy().astype(bool)
+    written = []
+    for i, (_, files) in enumerate(speakers.items()):
+        test_spk = i >= train_spk_num
+        # :37-40: a training speaker's first 100 files as listed; a test speaker's files sorted by name without the extension
+        files = sorted(files, key=lambda f: os.path.basename(f)[:-4]) if test_spk else list(files)[:100]
+        loaded = [(k, read_wav(f)) for k, f in enumerate(files) if f[-4:] == ".wav"]
+        feats = {}
+        for rate in sorted({sr for _, (sr, _) in loaded}):
+            ks = [k for k, (sr, _) in loaded if sr == rate]
+            f, v = front_end([w for _, (sr, w) in loaded if sr == rate], rate)
+            for j, k in enumerate(ks):
+                if v[j]:
+                    feats[k] = f[j]
+        utterances_spec, eval_spec = [], []
+        for k in sorted(feats):
+            dst = eval_spec if (test_spk and k >= enroll_num) else utterances_spec
+            dst.extend([np.ascontiguousarray(feats[k][0].T), np.ascontiguousarray(feats[k][1].T)])      # (nmels, frames), first then last
+        if test_spk:
+            _fill_slices(utterances_spec, enroll_num)
+            _fill_slices(eval_spec, eval_num)
+            utterances_spec.extend(eval_spec)
+        arr = np.array(utterances_spec)
+        if test_spk and arr.shape[0] != 2 * (enroll_num + eval_num):
+            raise RuntimeError("preprocess_tisv: speaker %d has %d slices, expected %d (data_preprocess.py:88)"
+                               % (i, arr.shape[0], 2 * (enroll_num + eval_num)))
+        path = os.path.join(d["test_path"], "speaker%d.npy" % (i - train_spk_num)) if test_spk else os.path.join(d["train_path"], "speaker%d.npy" % i)
+        np.save(path, arr)
+        written.append(path)
+    return written
+
+
+@torch.no_grad()
+def spoof_evaluation(cfg, net, enrol, genuine, spoof):
+    """The mixture test of ``test`` (train_speech_embedder.py:112-203) on features held in memory: ``enrol`` (N, ke, 2, frames, nmels),
+    ``genuine`` (N, kg, ...) and ``spoof`` (N, ks, ...) straight from ``TisvFrontEnd`` (kg == ks, as the sweep's halves assume), the
+    spoofing utterances never written to disk.  Per speaker the slices are laid out as ``speaker<N>.npy`` has them (enrolment, then
+    genuine, then spoof), embedded, compared (``cossim_eval``) and swept (``eer_sweep(spoof=True)``).  Returns the sweep's dict plus
+    the similarity matrix under "sim"."""
+    N = enrol.shape[0]
+    if not (genuine.shape[0] == N and spoof.shape[0] == N and genuine.shape[1] == spoof.shape[1]):
+        raise ValueError("spoof_evaluation: need the same speakers on all three sides and as many genuine as spoofing utterances")
+    fr, nm = enrol.shape[-2], enrol.shape[-1]
+    es1 = 2 * enrol.shape[1]
+    ver = torch.cat([genuine.reshape(N, -1, fr, nm), spoof.reshape(N, -1, fr, nm)], dim=1)
+    size_1 = es1 + ver.shape[1]
+    e_enr = net(enrol.reshape(N * es1, fr, nm).float().contiguous()).reshape(N, es1, -1)
+    e_ver = net(ver.reshape(N * (size_1 - es1), fr, nm).float().contiguous()).reshape(N, size_1 - es1, -1)
+    sim = cossim_eval(e_ver, e_enr.mean(dim=1))
+    out = eer_sweep(sim, size_1, es1, spoof=True)
+    out["sim"] = sim
+    return out

@@ -744,13 +744,14 @@ def plan_utterance_groups(n_speakers, n_texts, speakers_per_batch):
     return [[(s, u) for s in range(s0, min(s0 + S, n_speakers)) for u in range(n_texts)] for s0 in range(0, n_speakers, S)]
 
 
-def generate_test_utterances(cfg, current_time, eval_utt_num=20, speakers=None, texts=None, max_frames=None, speakers_per_batch=None):
+def generate_test_utterances(cfg, current_time, eval_utt_num=20, speakers=None, texts=None, max_frames=None, speakers_per_batch=None,
+                             return_waveforms=False):
     """generate_test_utterances.py:56-139: for every speaker, synthesize the first ``eval_utt_num`` sentences of TTS_TEXTS as
     ONE batch (texts zero-padded to a common length, :67-72; the speaker code repeated, :105) -- Text2Mel free run for
     MAX_FRAME_NUM further steps (:108-116), SSRN (:120), then per utterance Griffin-Lim(64), de-emphasis, trim(30 dB), clip to
     9 s, peak 0.75 and ``s<id>/s<id>_<nnn>.wav`` (:128-139).  Here the vocoder runs once per speaker on the whole batch
-    (spoofsv_amd.vocoder); only trim / clip / write stay per utterance on the host.  The Kaldi / GE2E / ASVspoof trial-list
-    bookkeeping of :141-260 is not reproduced.  ``speakers``: {name: (SPK_EMB_DIM,) array}; default: the .npy files of
+    (spoofsv_amd.vocoder); only trim / clip / write stay per utterance on the host.  The Kaldi / ASVspoof trial-list
+    bookkeeping of :141-260 is not reproduced; the GE2E features of the written files are ``ge2e_harness.preprocess_tisv``.  ``speakers``: {name: (SPK_EMB_DIM,) array}; default: the .npy files of
     SPK_EMB_DIR.  Returns {speaker: [wav paths]}.
 
     ``speakers_per_batch`` (config key SYNTH_SPEAKERS_PER_BATCH, default 1 = the loop above, unchanged): with S > 1 the speakers are
@@ -760,7 +761,12 @@ def generate_test_utterances(cfg, current_time, eval_utt_num=20, speakers=None, 
     its own size.  A frame of the wide step costs the same 1.1-1.3 ms for 20 items and for 2,160 (the per-speaker
     loop costs 0.27 ms per frame and speaker), so small groups LOSE: measured 0.24x at S = 1, 0.90x at S = 4, 3.5x at S = 16, 11.7x at
     S = 54, 23x at S = 108.  Use S >= 16 -- the smallest measured value at which the grouped run is not slower -- and as many speakers as
-    the device memory takes (``synth.wide_synth_bytes``: 5.4 MB per item at 326 frames, 11.3 GiB for 108 speakers)."""
+    the device memory takes (``synth.wide_synth_bytes``: 5.4 MB per item at 326 frames, 11.3 GiB for 108 speakers).
+
+    ``return_waveforms=True`` keeps trim / clip / peak on the device (``ssv_trim_bounds``, ``ssv_segment_peak``) and returns
+    ``(paths, {speaker: (waveforms (U, at most 9 s) float32 zero-padded, lengths (U,) int32)})`` -- device tensors, what is written to the files --
+    so that ``ge2e_harness.spoof_evaluation`` can be fed without reading them back.  The device trim sums frame energies in fp32, the
+    host loop in float64: where a frame sits at the threshold the bounds may differ by one 512-sample hop."""
     from scipy.io import wavfile
     from .vocoder import Vocoder, trim_silence
     dev = _device()
@@ -811,25 +817,37 @@ def generate_test_utterances(cfg, current_time, eval_utt_num=20, speakers=None, 
             for i, spk in enumerate(members):
                 yield spk, Yg[i * U:(i + 1) * U].contiguous()
 
+    waves = {}
     with torch.no_grad():
         for spk, Y in mels():
             resident.ensure(m2, ops._stream())
             lin = m2(Y).contiguous()
             wav = voc.spectrogram2wav(lin, cfg, n_iter=cfg.get("GRIFFIN_LIM_ITERS", 64), graph=cfg.get("SYNTH_GRAPH", False),
-                                      peak=None).cpu().numpy()
+                                      peak=None)
+            if return_waveforms:
+                from . import sv_frontend
+                full = torch.full((wav.shape[0],), wav.shape[1], dtype=torch.int32, device=wav.device)
+                seg, seg_n = sv_frontend.segment_peak(wav.contiguous(), sv_frontend.trim_bounds(wav.contiguous(), full, 30), min(9 * sr, wav.shape[1]), 0.75)
+                waves[spk] = (seg, seg_n)
+                seg_host, seg_len = seg.cpu().numpy(), seg_n.cpu().numpy()
+            else:
+                wav = wav.cpu().numpy()
             sdir = os.path.join(save_dir, "s" + spk[1:])
             os.makedirs(sdir, exist_ok=True)
             paths = []
             for k in range(len(ids)):
-                y, _ = trim_silence(wav[k], 30)
-                y = y[:9 * sr]
-                if len(y):
-                    y = (y / np.max(y) * 0.75).astype(np.float32)
+                if return_waveforms:
+                    y = seg_host[k, :seg_len[k]]
+                else:
+                    y, _ = trim_silence(wav[k], 30)
+                    y = y[:9 * sr]
+                    if len(y):
+                        y = (y / np.max(y) * 0.75).astype(np.float32)
                 path = os.path.join(sdir, "s{}_{}.wav".format(spk[1:], str(k + 1).zfill(3)))
                 wavfile.write(path, sr, y)
                 paths.append(path)
             out[spk] = paths
-    return out
+    return (out, waves) if return_waveforms else out
 
 
 def extract_features(wav_paths, cfg, spec_dir):
