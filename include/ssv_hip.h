@@ -49,7 +49,8 @@ const char* ssv_last_error(void); /* thread-local, valid until the next failing 
  * is max |x(b)| -- partial maxima, in any partition.  The LayerNorm / gate kernels write such a list for their output as
  * a by-product (ssv_amax_rows(L) entries per item: one per kernel tile, unused ones zeroed), ssv_absmax computes one for any tensor, and
  * every entry below that takes `*_amax, *_namax` arguments accepts NULL, 0: it then computes the list itself in its
- * workspace (one extra small launch).  Outside mode 2 the arguments are ignored (amax outputs are still written). */
+ * workspace (one extra small launch).  Outside mode 2 the arguments are ignored (amax outputs are still written, except y_amax of
+ * ssv_deconv1d_k2s2_fwd: mode 2 only).  A NaN element does not enter a list (fmaxf drops it): the entry is the maximum of the others. */
 int ssv_set_precision(int mode);
 int ssv_get_precision(void);
 int ssv_amax_rows(int L);         /* entries per batch item of the lists the LayerNorm / gate kernels write: 4 * ceil(L / 64) */
@@ -263,7 +264,9 @@ int ssv_attention_apply(const float* v, long kv_bs, const float* a, int a_T, flo
  * y(b,o,2t+j) = bias[o] + sum_c w[c,o,j] x(b,c,t). */
 size_t ssv_deconv1d_k2s2_fwd_workspace(int Cin, int Cout);   /* pre-split weights (when no resident planes are given) */
 /* ABI 7: w_packed = the resident planes of the 1x1 weight w.view(Cin, 2 Cout, 1) (ssv_conv_pack_multi; NULL: split here) -- the forward is ONE product over
- * 2 Cout rows whose epilogue interleaves the row pairs --, and y_amax (may be NULL) receives y's operand-scale list, y_namax entries per item. */
+ * 2 Cout rows whose epilogue interleaves the row pairs --, and y_amax (may be NULL) receives y's operand-scale list, y_namax entries per item
+ * (mode 2 only; the other modes leave it untouched.  One entry per tile of the product; with more tiles per item than y_namax -- long sequences, small batches --
+ * the product runs without the list and one ssv_absmax launch over y fills it: every length works). */
 int ssv_deconv1d_k2s2_fwd(const float* x, long x_bs, const float* x_amax, int x_namax, const float* w, const void* w_packed, const float* bias,
                           float* y, long y_bs, float* y_amax, int y_namax, int B, int Cin, int Cout, int L, void* ws, size_t ws_bytes, ssv_stream_t stream);
 size_t ssv_deconv1d_k2s2_bwd_workspace(int B, int Cin, int Cout);
