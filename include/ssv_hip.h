@@ -465,6 +465,30 @@ int ssv_power_mel_log(const float* spec, const float* mel, float* out, int R, in
  * len = min(end - start, clip), zeros after; n_out[b] = len.  The maximum, not the absolute maximum, as the reference has it. */
 int ssv_segment_peak(const float* y, const int* bounds, float* out, int* n_out, int B, int n_max, int clip, float peak, ssv_stream_t stream);
 
+/* ---- Whole-utterance d-vectors: every frame of every voiced span -> windows -> partition means (additions; ABI version unchanged) ----
+ * Replaces GE2E/dvector_create.py:38-73 (`get_STFTs`: `librosa.core.stft` of every concatenated voiced segment, `S[:, j:j+24]` every 12
+ * frames; `align_embeddings`: `np.average` over partitions of about 0.4 s) for ragged batches.  The host plans (which spans, which
+ * windows, which partitions: spoofsv_amd/dvector.py) and ships int tables; a table entry that does not fit the buffers is skipped by
+ * the kernel that reads it, never followed out of bounds.  Between ssv_span_frames and ssv_gather_windows run ssv_conv1d_fwd (k = 1,
+ * the Fourier basis) and ssv_power_mel_log as above; between ssv_gather_windows and ssv_segment_mean the embedder.
+ * Codes: NULL pointers, non-positive sizes, hop > n_fft, window * hop <= n_fft / 2: -1; a hop / n_fft beyond the LDS tile: -2. */
+/* All centred frames of librosa.stft(seg, n_fft, hop) (:43) for the spans of a tile table.  tiles (n_tiles, 6) int on the device:
+ * (row, span start, span end, first frame of the tile in its span, its first compact frame index g0, frame count <= 64), seg =
+ * y[row][start:end], frame f = samples f * hop - n_fft / 2 + i (i < n_fft) of seg, reflected once at seg's own ends
+ * (np.pad(mode="reflect") of the segment, not of the row; spans are at least window * hop > n_fft / 2 samples long).  Compact frame
+ * g in [g_base, g_base + n_frames) goes to fr (R, n_fft, Tc) as column (g - g_base) % Tc of item (g - g_base) / Tc -- the layout
+ * ssv_conv1d_fwd reads -- frames of a tile outside that range are left out, the columns past n_frames in the last item are zeroed:
+ * (R - 1) * Tc < n_frames <= R * Tc.  A workgroup stages one tile's samples in LDS: (64 - 1) * hop + n_fft <= 12288 floats. */
+int ssv_span_frames(const float* y, const int* tiles, float* fr, int B, int n_max, int n_tiles, int n_fft, int hop, int window, int Tc,
+                    int R, int g_base, int n_frames, ssv_stream_t stream);
+/* out (Nw, window, nmels)[w] = mel[g0[w] : g0[w] + window] of the frames-major log-mel array mel (G, nmels) (:48-52, transposed as :99
+ * does), g0 (Nw) int on the device; 16-byte copies when nmels % 4 == 0.  A window that does not fit mel is written as zeros. */
+int ssv_gather_windows(const float* mel, const int* g0, float* out, int G, int Nw, int window, int nmels, ssv_stream_t stream);
+/* out (P, D)[p] = mean of rows offs[p] .. offs[p + 1] - 1 of e (Nw, D) (:70-72), offs (P + 1) int on the device; rows added in ascending
+ * order in fp32 whatever the launch looks like; normalize != 0: the mean is divided by its L2 norm afterwards (the reference does not;
+ * the utterance-level d-vector of the GE2E paper does).  An empty partition gives zeros. */
+int ssv_segment_mean(const float* e, const int* offs, float* out, int Nw, int P, int D, int normalize, ssv_stream_t stream);
+
 /* ---- Second order, for the critics' gradient penalty ------------------------------------------
  * train/adversarial_wasserstein_gp.py:300-308 differentiates the critic's input gradient
  * (`autograd.grad(..., create_graph=True)` then `loss.backward()`), so the LayerNorm / highway-gate BACKWARD kernels need

@@ -314,3 +314,90 @@ def spoof_evaluation(cfg, net, enrol, genuine, spoof):
     out = eer_sweep(sim, size_1, es1, spoof=True)
     out["sim"] = sim
     return out
+
+
+@torch.no_grad()
+def dvector_create(cfg, speaker_folders, vad=None, out_dir=".", utterances_per_batch=64, read=read_wav, net=None):
+    """GE2E/dvector_create.py:75-122 with everything after the VAD on the device (``spoofsv_amd.dvector``).  ``speaker_folders``: the
+    speakers' folders in the order to walk them (the reference globs ``hp.unprocessed_data``); a folder's index is its label, its
+    ``.wav`` files are taken in ``os.listdir`` order, sorted here so that a run can be repeated.  ``vad(path) -> times`` returns what
+    ``VAD_chunk`` returns first (VAD_segments.py:130-150; webrtcvad itself is not part of this project); an empty list prints the
+    reference's "No voice activity detected" and skips the file.  ``vad=None``: one span per file, its ``trim_bounds(..., 30)``.
+    Files are decoded by ``read`` (path -> (rate, waveform)), resampled on the device when their rate is not cfg["data"]["sr"], and
+    embedded ``utterances_per_batch`` at a time, across files and speakers, in one device pass each.  The embedder is ``net`` or the
+    checkpoint cfg["model"]["model_path"].
+
+    Writes ``train_sequence.npy`` / ``train_cluster_id.npy`` / ``test_sequence.npy`` / ``test_cluster_id.npy`` under ``out_dir`` as the
+    reference does: float64 rows (``align_embeddings`` fills an ``np.zeros`` array), string ids, the training files after the FIRST
+    folder whose index i satisfies ``i > (total // 10) * 9`` (:78, :110 -- that folder included), the rest as test.  Where nothing is
+    left for a file set the reference's ``np.concatenate([])`` raises; here an empty (0, proj) array and an empty id array are written.
+    A file none of whose spans gives a window (the reference crashes there, in ``np.stack([])``) contributes no row.  Returns the four paths."""
+    from .dvector import DvectorExtractor, spans_from_vad
+    from .sv_frontend import TisvFrontEnd
+    d = cfg["data"]
+    fe = TisvFrontEnd.from_config(cfg)
+    if net is None:
+        net = _load(cfg, cfg["model"]["model_path"], fe.device)
+    ex = DvectorExtractor(fe, net)
+    proj = net.dims[3]
+    folders = list(speaker_folders)
+    files = [(i, os.path.join(folder, f)) for i, folder in enumerate(folders) for f in sorted(os.listdir(folder)) if f[-4:] == ".wav"]
+    rows_of = {}                                                 # file index -> (rows, proj) float64, absent: no voice activity
+    for lo in range(0, len(files), max(1, int(utterances_per_batch))):
+        chunk = list(range(lo, min(len(files), lo + max(1, int(utterances_per_batch)))))
+        loaded = [read(files[k][1]) for k in chunk]
+        waves = [None] * len(chunk)
+        for rate in sorted({sr for sr, _ in loaded}):
+            js = [j for j, (sr, _) in enumerate(loaded) if sr == rate]
+            y, n = pad_batch([loaded[j][1] for j in js], fe.device)
+            if rate != d["sr"]:
+                y, n = fe.resample(y, n, rate)
+            for j, m in zip(js, n.cpu().tolist()):
+                waves[j] = (y, js.index(j), m)
+        n_max = max(1, max(m for _, _, m in waves))
+        y16 = torch.zeros((len(chunk), n_max), dtype=torch.float32, device=fe.device)
+        for j, (y, r, m) in enumerate(waves):
+            y16[j, :m] = y[r, :m]
+        n16 = torch.tensor([m for _, _, m in waves], dtype=torch.int32, device=fe.device)
+        spans, voiced = None, [True] * len(chunk)
+        if vad is not None:
+            spans = []
+            for j, k in enumerate(chunk):
+                times = vad(files[k][1])
+                voiced[j] = len(times) > 0
+                spans.append(spans_from_vad(times, d["sr"], waves[j][2]))
+        seq, rows = ex(y16, n16, spans)
+        seq = seq.cpu().numpy().astype(np.float64)
+        at = 0
+        for j, k in enumerate(chunk):
+            if voiced[j]:
+                rows_of[k] = seq[at:at + rows[j]]
+            at += rows[j]
+    # the reference's loop (:84-122) over what the device made of every file
+    train_speaker_num = (len(folders) // 10) * 9
+    sequence, cluster_id, count, train_saved = [], [], 0, False
+    paths = [os.path.join(out_dir, n + ".npy") for n in ("train_sequence", "train_cluster_id", "test_sequence", "test_cluster_id")]
+    os.makedirs(out_dir, exist_ok=True)
+
+    def save(seq_path, id_path):
+        np.save(seq_path, np.concatenate(sequence, axis=0) if sequence else np.zeros((0, proj)))
+        np.save(id_path, np.asarray(cluster_id, dtype=str))
+    by_folder = {}
+    for k, (i, _) in enumerate(files):
+        by_folder.setdefault(i, []).append(k)
+    for i in range(len(folders)):
+        for k in by_folder.get(i, []):
+            if k not in rows_of:
+                print("No voice activity detected")
+                continue
+            sequence.append(rows_of[k])
+            cluster_id.extend([str(i)] * rows_of[k].shape[0])
+            count += 1
+            if count % 100 == 0:
+                print("Processed {0}/{1} files".format(count, len(folders)))
+        if not train_saved and i > train_speaker_num:
+            save(paths[0], paths[1])
+            train_saved = True
+            sequence, cluster_id = [], []
+    save(paths[2], paths[3])
+    return paths
