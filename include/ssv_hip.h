@@ -489,6 +489,31 @@ int ssv_gather_windows(const float* mel, const int* g0, float* out, int G, int N
  * the utterance-level d-vector of the GE2E paper does).  An empty partition gives zeros. */
 int ssv_segment_mean(const float* e, const int* offs, float* out, int Nw, int P, int D, int normalize, ssv_stream_t stream);
 
+/* ---- Corpus spectrograms for ragged batches: trimmed waveforms -> the collated (mel, linear) training batch (additions; ABI version
+ * unchanged) -------------------------------------------------------------------------------------------------------------------------
+ * Replaces data/dataset.py:94-118 (`librosa.effects.trim(speech, 22)`, the pre-emphasis `np.append`, `librosa.stft`, `np.dot(mel_filterbank,
+ * lin_spec)`, both normalisations, the time reduction) and the zero padding of collate_pad_2 / collate_pad_3 (:215-258) for B utterances
+ * at once: waveforms (B, n_max) with (start, end) bounds (B, 2) int ON THE DEVICE, as ssv_trim_bounds (top_db = 22) writes them; resampling
+ * in front (metagen.py:29-62) is ssv_resample_sinc.  Between the two entries run ssv_conv1d_fwd (k = 1, the Fourier basis), ssv_complex_abs,
+ * ssv_conv1d_fwd (the mel basis) and, for the default normalisation, ssv_rowmax.
+ * Codes: NULL pointers, non-positive sizes, an odd n_fft, hop > n_fft, a T_max below 1 + n_max / hop, r * RT_max > T_max, an output that is
+ * its own input: -1; a hop / n_fft whose 16-frame tile does not fit the LDS image (12,800 floats): -2.  All checked before any launch. */
+/* data/dataset.py:95-97 up to the DFT's input.  seg = y[b][start:end], len = end - start; p[0] = seg[0], p[i] = seg[i] - preemph * seg[i-1]
+ * (:96, one fused multiply-add; the sample before `start` is not read); fr (B, n_fft, T_max)[b][i][t] = np.pad(p, n_fft / 2, "reflect")
+ * [t * hop + i] for t < n_frames[b] = 1 + len / hop (librosa.stft, center=True), zeros for t >= n_frames[b].  A segment of
+ * len <= n_fft / 2 (an empty one included) has nothing to reflect from: n_frames[b] = 0 and all-zero frames. */
+int ssv_preemph_frames_ragged(const float* y, const int* bounds, float* fr, int* n_frames, int B, int n_max, int n_fft, int hop, int T_max,
+                              float preemph, ssv_stream_t stream);
+/* data/dataset.py:101-118 for magnitudes lin (B, F, T_max) and mel (B, M, T_max) whose columns >= n_frames[b] are zero, into the collated
+ * layout: rt[b] = n_frames[b] / r (:115); mel_out (B, M, RT_max)[b][m][k] = norm(mel[b][m][k * r]) for k < rt[b] (:116-117); lin_out
+ * (B, F, r * RT_max)[b][f][c] = norm(lin[b][f][c]) for c < r * rt[b] (:118); exact zeros after, as collate_pad_* pads.
+ * log_feature == 0: norm(x) = (x / max)^power with max_lin[b] / max_mel[b] (B) the item's maxima (:108-112; ssv_rowmax over the padded
+ * item); a maximum of 0 gives zeros where the reference gives NaN.  log_feature != 0: norm(x) = clip((20 log10(max(1e-5, x)) - ref_db +
+ * max_db) / max_db, 1e-8, 1) (:102-105); the maxima are not read and may be NULL. */
+int ssv_corpus_normalize_pack(const float* lin, const float* mel, const float* max_lin, const float* max_mel, const int* n_frames,
+                              float* mel_out, float* lin_out, int* rt, int B, int F, int M, int T_max, int RT_max, int r, int log_feature,
+                              float power, float ref_db, float max_db, ssv_stream_t stream);
+
 /* ---- Second order, for the critics' gradient penalty ------------------------------------------
  * train/adversarial_wasserstein_gp.py:300-308 differentiates the critic's input gradient
  * (`autograd.grad(..., create_graph=True)` then `loss.backward()`), so the LayerNorm / highway-gate BACKWARD kernels need

@@ -115,7 +115,13 @@ class CorpusSource:
     {wav,txt}.path.{train,validate}`` (one path per line; a wav path ends in ``pXXX/pXXX_NNN.wav``), one-line transcripts,
     ``SPK_EMB_DIR/pXXX.npy`` speaker codes.  Spectrograms come from the ``.npy`` cache of data/dataset.py:85-91; files that
     are not cached yet are extracted once, up front, on the GPU (``extract_features``).  Batches are zero-padded to their own
-    longest item, as the collate functions do ('P' = id 0 pads the text)."""
+    longest item, as the collate functions do ('P' = id 0 pads the text).
+
+    Optional config key CORPUS_FEATURES: absent or "cache" is the path above.  "batched" fills the missing cache entries through
+    ``extract_features_batched`` (ragged batches, resampling included).  "device" reads and writes no spectrogram cache: an item
+    is its waveform, a batch's waveforms are padded and uploaded once and ``corpus_features.CorpusFeatureExtractor`` turns them into
+    ``data_0`` / ``data_1`` / ``data_3`` ON THE DEVICE, in the layout and zero padding of the collated cached items (texts and speaker
+    codes stay host tensors, as today); ``last_rt`` then holds the batch's reduced frame counts, copied to the host once per batch."""
 
     def __init__(self, cfg, step, pattern, mode, batch_size, spec_dir=None, seed=0, rank=0, world=1, stage=None):
         self.cfg, self.step, self.mode, self.B = cfg, step, mode, batch_size
@@ -132,15 +138,40 @@ class CorpusSource:
         if len(self.wavlist) != len(self.txtlist):
             raise RuntimeError("corpus lists differ in length: %d wav paths, %d transcripts" % (len(self.wavlist), len(self.txtlist)))
         self.cache = spec_dir or (os.path.join(cfg["SRC_ROOT_DIR"], "spec_cache") + os.sep)
+        self.features = cfg.get("CORPUS_FEATURES", "cache")
+        if self.features not in ("cache", "batched", "device"):
+            raise ValueError("CORPUS_FEATURES must be 'cache', 'batched' or 'device', got %r" % (self.features,))
+        self.extractor, self.last_rt = None, None
+        if self.features == "device":
+            from .corpus_features import CorpusFeatureExtractor
+            self.extractor = CorpusFeatureExtractor(cfg, "cuda")              # raises without a ROCm device: no fallback
+            return
         missing = [w for w in self.wavlist if not os.path.exists(self.cache + w[-17:-4] + "_mel.npy")]
-        if missing:
+        if missing and self.features == "batched":
+            extract_features_batched(missing, cfg, self.cache)
+        elif missing:
             extract_features(missing, cfg, self.cache)
 
     def __len__(self):
         per = self.B * self.world
         return (len(self.wavlist) + per - 1) // per
 
+    def _item_wave(self, idx):
+        """CORPUS_FEATURES = "device": the item without its spectrograms -- the decoded waveform and its rate instead."""
+        sr, y = _read_wav(self.wavlist[idx])
+        out = {"_wav": y, "_sr": sr}
+        if self.step == "train_ssrn":
+            return out
+        with open(self.txtlist[idx]) as f:
+            text = f.readline().strip()
+        out["data_1"] = torch.tensor(text2id(text, self.cfg["VOCABULARY"]), dtype=torch.long).view(1, -1)
+        spk = np.load(os.path.join(self.cfg["SPK_EMB_DIR"], self.wavlist[idx][-12:-8] + ".npy"))
+        out["data_2"] = torch.from_numpy(np.asarray(spk, dtype=np.float32)).view(-1, 1)
+        return out
+
     def _item(self, idx):
+        if self.features == "device":
+            return self._item_wave(idx)
         key = self.wavlist[idx][-17:-4]
         out = {"data_0": torch.from_numpy(np.load(self.cache + key + "_mel.npy")).float()}
         if self.step == "train_ssrn":
@@ -160,7 +191,40 @@ class CorpusSource:
         width = max(it[key].shape[-1] for it in items)
         return torch.stack([torch.nn.functional.pad(it[key], (0, width - it[key].shape[-1])) for it in items], 0)
 
-    def __iter__(self):
+    def _collate(self, items):
+        if self.features != "device":
+            return {key: (torch.stack([it[key] for it in items], 0) if key == "data_2" else self._pad_stack(items, key)) for key in items[0]}
+        rates = sorted({it["_sr"] for it in items})
+        if len(rates) != 1:
+            raise RuntimeError("CORPUS_FEATURES='device': the files of one batch must share a sampling rate, got %s" % rates)
+        n_max = max(1, max(len(it["_wav"]) for it in items))
+        wav = torch.zeros((len(items), n_max), dtype=torch.float32)
+        for b, it in enumerate(items):
+            wav[b, :len(it["_wav"])] = torch.from_numpy(it["_wav"])
+        out = {"_wav": wav, "_len": torch.tensor([len(it["_wav"]) for it in items], dtype=torch.int32), "_sr": rates[0]}
+        if "data_1" in items[0]:
+            out["data_1"] = self._pad_stack(items, "data_1")
+            out["data_2"] = torch.stack([it["data_2"] for it in items], 0)
+        return out
+
+    def finish_batch(self, hb):
+        """CORPUS_FEATURES = "device": a host batch of ``host_batches`` -> the training batch.  One upload of the padded waveforms, the
+        extractor, one copy of the B frame counts back (``last_rt``).  Batch preparation: call it on the thread that issues the training
+        step (``Prefetcher`` does), outside any captured graph."""
+        dev = self.extractor.device
+        mel, lin, self.last_rt = self.extractor.collated(hb["_wav"].to(dev, non_blocking=True), hb["_len"].to(dev, non_blocking=True), hb["_sr"])
+        out = {"data_0": mel}
+        if self.step == "train_ssrn":
+            out["data_1"] = lin
+            return out
+        out["data_1"], out["data_2"] = hb["data_1"], hb["data_2"]
+        if self.step == "synthesize" and self.mode != "validate":      # data/dataset.py:131-132
+            out["data_3"] = lin
+        return out
+
+    def host_batches(self):
+        """The batches of ``__iter__`` before any device work (what a prefetching thread may run ahead): the finished batch in the cache
+        modes, the padded waveforms with texts and speaker codes in "device" mode."""
         n = len(self.wavlist)
         order = np.arange(n)
         if self.mode == "train":                                    # DataLoader(shuffle=True): a fresh permutation per epoch
@@ -175,8 +239,11 @@ class CorpusSource:
                 idx = order[np.arange(i * per + self.rank * self.B, i * per + (self.rank + 1) * self.B) % n]
             else:
                 idx = order[i * per:(i + 1) * per]                     # one process: the reference's partial last batch (drop_last=False)
-            items = [self._item(int(k)) for k in idx]
-            yield {key: (torch.stack([it[key] for it in items], 0) if key == "data_2" else self._pad_stack(items, key)) for key in items[0]}
+            yield self._collate([self._item(int(k)) for k in idx])
+
+    def __iter__(self):
+        for hb in self.host_batches():
+            yield self.finish_batch(hb) if self.features == "device" else hb
 
 
 class BatchSource:
@@ -232,6 +299,17 @@ class BatchSource:
             return {"data_0": mel, "data_1": lin}
         raise RuntimeError("cached text2mel batches need the corpus transcripts; use synthetic batches")
 
+    @property
+    def device_features(self):
+        """True when batches are finished on the device by ``finish_batch`` (a corpus with CORPUS_FEATURES = "device")."""
+        return self.corpus is not None and self.corpus.features == "device"
+
+    def host_batches(self):
+        return self.corpus.host_batches()
+
+    def finish_batch(self, hb):
+        return self.corpus.finish_batch(hb)
+
     def __iter__(self):
         if self.corpus is not None:
             yield from self.corpus
@@ -244,7 +322,10 @@ class Prefetcher:
     """Iterate over a batch source with the host work (file reads / synthetic generation, padding) done one or two batches
     ahead on a background thread into pinned memory, and the host-to-device copies issued without blocking: the role of the
     reference's multi-worker DataLoader (train/ordinary.py:199-200), sized for one process per GPU.  Yields the same dicts,
-    already on ``device``, in the same order."""
+    already on ``device``, in the same order.  Tensors that are on a device already pass through unchanged.  A source whose
+    ``device_features`` is true (CORPUS_FEATURES = "device") is read through ``host_batches`` on the background thread -- file
+    decoding and padding -- and each batch is finished by ``finish_batch`` HERE, on the consuming thread: the extractor issues library
+    calls and switches the library's arithmetic mode around its transforms, which must not interleave with the training step's calls."""
 
     def __init__(self, source, device, depth=2):
         self.source, self.device, self.depth = source, device, depth
@@ -259,10 +340,12 @@ class Prefetcher:
         pin = torch.cuda.is_available() and self.device.type == "cuda"
         stop = object()
 
+        finish = self.source.finish_batch if getattr(self.source, "device_features", False) else None
+
         def work():
             try:
-                for sp in self.source:
-                    q.put({k: (v.pin_memory() if pin else v) for k, v in sp.items()})
+                for sp in (self.source.host_batches() if finish is not None else self.source):
+                    q.put({k: (v.pin_memory() if pin and torch.is_tensor(v) and not v.is_cuda else v) for k, v in sp.items()})
                 q.put(stop)
             except BaseException as e:          # surface loader errors in the consumer
                 q.put(e)
@@ -275,6 +358,8 @@ class Prefetcher:
                 break
             if isinstance(item, BaseException):
                 raise item
+            if finish is not None:
+                item = finish(item)
             yield {k: v.to(self.device, non_blocking=pin) for k, v in item.items()}
         th.join()
 
@@ -848,6 +933,71 @@ def generate_test_utterances(cfg, current_time, eval_utt_num=20, speakers=None, 
                 paths.append(path)
             out[spk] = paths
     return (out, waves) if return_waveforms else out
+
+
+def _read_wav(path):
+    """``scipy.io.wavfile`` decoding with the conventions of ``extract_features``: (rate, mono float32 waveform); channels are averaged,
+    integer PCM is scaled by its width."""
+    from scipy.io import wavfile
+    sr, y = wavfile.read(path)
+    if y.ndim > 1:
+        y = y.mean(axis=1)                                   # librosa.load(mono=True)
+    if y.dtype.kind in "iu":
+        y = y.astype(np.float32) / float(1 << (8 * y.dtype.itemsize - 1))
+    return int(sr), np.ascontiguousarray(y, dtype=np.float32)
+
+
+def extract_features_batched(wav_paths, cfg, spec_dir, utterances_per_batch=32, extractor=None):
+    """``extract_features`` for ragged batches (``corpus_features.CorpusFeatureExtractor``): the same cache files
+    ``<spec_dir>/<pXXX>/<pXXX_NNN>_{mel,lin}.npy`` from the same decoding, ``utterances_per_batch`` files per pass -- one upload of the
+    padded waveforms, trim, pre-emphasis, |STFT|, mel, normalisation and reduction for the whole batch on the device, ONE copy of the result back,
+    then the files.  Files are grouped by sampling rate (a batch shares one) in their given order; a rate other than SAMPLING_RATE is
+    resampled first (metagen.py:29-62: resample, then trim; an unsupported ratio raises ``ValueError``), which ``extract_features`` does
+    not do -- for such files it transforms the signal at its native rate.  The trim runs on the device in fp32 where ``extract_features``
+    trims on the host in float64: where a frame sits at the 22 dB threshold the bounds may differ by one 512-sample hop.
+    Returns the list of (mel shape, lin shape) in input order; a file too short to give a frame (fewer than ``n_fft // 2 + 1`` samples
+    after the trim, or fewer than REDUCTION frames) writes nothing, is named in a warning, and has ``None`` in the list.
+
+    Speed against ``extract_features``: not measured yet; tools/bench_corpus_features.py measures it and writes profiles/corpus_features.txt."""
+    import warnings
+    from .corpus_features import CorpusFeatureExtractor
+    if int(utterances_per_batch) < 1:
+        raise ValueError("extract_features_batched: utterances_per_batch must be at least 1")
+    ex = extractor if extractor is not None else CorpusFeatureExtractor(cfg, "cuda")      # raises without a ROCm device: no fallback
+    r = cfg["COARSE_MELSPEC"]["REDUCTION"]
+    shapes = [None] * len(wav_paths)
+    pending = {}                                                 # rate -> [(index, waveform)]
+
+    def flush(sr, group):
+        n_max = max(1, max(len(y) for _, y in group))
+        wav = torch.zeros((len(group), n_max), dtype=torch.float32)
+        for b, (_, y) in enumerate(group):
+            wav[b, :len(y)] = torch.from_numpy(y)
+        lens = torch.tensor([len(y) for _, y in group], dtype=torch.int32)
+        mel, lin, rt = ex.to_host(wav.to(ex.device), lens.to(ex.device), sr)
+        for b, (i, _) in enumerate(group):
+            path = wav_paths[i]
+            if rt[b] <= 0:
+                warnings.warn("extract_features_batched: %s is too short to give a frame after the trim; nothing written" % path)
+                continue
+            key = path[-17:-4]                                   # 'pXXX/pXXX_NNN', data/dataset.py:85
+            os.makedirs(os.path.join(spec_dir, os.path.dirname(key)), exist_ok=True)
+            m, l = np.ascontiguousarray(mel[b, :, :rt[b]]), np.ascontiguousarray(lin[b, :, :r * rt[b]])
+            np.save(os.path.join(spec_dir, key + "_mel.npy"), m)
+            np.save(os.path.join(spec_dir, key + "_lin.npy"), l)
+            shapes[i] = (tuple(m.shape), tuple(l.shape))
+
+    for i, path in enumerate(wav_paths):
+        sr, y = _read_wav(path)
+        group = pending.setdefault(sr, [])
+        group.append((i, y))
+        if len(group) == int(utterances_per_batch):
+            flush(sr, group)
+            pending[sr] = []
+    for sr, group in pending.items():
+        if group:
+            flush(sr, group)
+    return shapes
 
 
 def extract_features(wav_paths, cfg, spec_dir):
