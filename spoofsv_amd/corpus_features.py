@@ -14,22 +14,18 @@ utterance's few hundred.  It runs in exact fp32 (``dft_mode="fp32"``) by default
 does not depend on its batch mates (the split-fp16 mode scales an operand tile by its own largest magnitude).
 There is no CPU fallback: a non-ROCm tensor raises.
 """
-import ctypes
-from fractions import Fraction
+import contextlib
 
 import numpy as np
 import torch
 
 from . import _lib, ops
-from .sv_frontend import _check_wave, polyphase_bank
+from .ops import _p
+from .wave import Resampler, check_wave, fp32_products, resampled_width, rocm_device, trim_bounds
 
 _F32, _I32 = torch.float32, torch.int32
 TRIM_TOP_DB = 22.0        # data/dataset.py:95
 _ALIGN = 64               # floats: every arena view starts on a 256-byte line
-
-
-def _p(t):
-    return ctypes.c_void_p(t.data_ptr())
 
 
 def feature_lengths(n, n_fft, hop, r):
@@ -40,11 +36,6 @@ def feature_lengths(n, n_fft, hop, r):
     return T, T // r, r * (T // r)
 
 
-def _ratio(orig_sr, sr):
-    f = Fraction(int(sr), int(orig_sr))
-    return f.numerator, f.denominator
-
-
 def _dims(B, n_max, cfg, orig_sr=None):
     sr = int(cfg["SAMPLING_RATE"])
     N, hop = int(cfg["STFT"]["FFT_LENGTH"]), int(cfg["STFT"]["HOP_LENGTH"])
@@ -53,8 +44,7 @@ def _dims(B, n_max, cfg, orig_sr=None):
     if B <= 0 or n_max <= 0:
         raise ValueError("need B > 0 and n_max > 0")
     resampled = orig_sr is not None and int(orig_sr) != sr
-    up, down = _ratio(orig_sr, sr) if resampled else (1, 1)
-    m_max = int(np.ceil(n_max * (float(up) / float(down)))) if resampled else n_max
+    m_max = resampled_width(n_max, orig_sr, sr) if resampled else n_max
     T_max = max(1 + m_max // hop, r)
     return dict(B=B, n_max=n_max, m_max=m_max, resampled=resampled, N=N, hop=hop, F=N // 2 + 1, M=M, r=r, T_max=T_max, RT_max=T_max // r)
 
@@ -92,11 +82,9 @@ class CorpusFeatureExtractor:
     or "default" (the library's arithmetic mode in force, split-fp16 unless changed)."""
 
     def __init__(self, cfg, device="cuda", dft_mode="fp32"):
-        dev = torch.device(device)
-        if dev.type != "cuda" or not torch.cuda.is_available():
-            raise RuntimeError("spoofsv_amd.corpus_features: needs a ROCm device (no CPU fallback exists), got %s" % dev)
-        if dev.index is None:
-            dev = torch.device("cuda", torch.cuda.current_device())
+        if not torch.cuda.is_available():
+            raise RuntimeError("spoofsv_amd.corpus_features: needs a ROCm device (no CPU fallback exists), got %s" % torch.device(device))
+        dev = rocm_device(device, "corpus_features")
         if dft_mode not in ("fp32", "default"):
             raise ValueError("dft_mode must be 'fp32' or 'default'")
         from .vocoder import Vocoder
@@ -110,21 +98,11 @@ class CorpusFeatureExtractor:
         self.ref_db, self.max_db = float(cfg.get("REF_DB", 20)), float(cfg.get("MAX_DB", 100))
         self.voc = Vocoder(self.n_fft, self.hop, dev)                       # the Fourier bases and their resident planes
         self.w_mel = self.voc.mel_basis(self.sr, self.M)
-        self._banks = {}
+        self.resampler = Resampler(self.sr, dev)
         self._arena = None
         self.nbytes = 0
 
     # ------------------------------------------------------------------ buffers
-    def _bank(self, orig_sr, upload=True):
-        key = int(orig_sr)
-        b = self._banks.get(key)
-        if b is None:
-            bank, up, down, left = polyphase_bank(key, self.sr)             # ValueError for a ratio the kernel's tiles cannot take
-            b = self._banks[key] = [np.ascontiguousarray(bank, dtype=np.float32), up, down, left, bank.shape[1]]
-        if upload and not torch.is_tensor(b[0]):
-            b[0] = torch.from_numpy(b[0]).to(self.device)
-        return b
-
     def _views(self, d):
         """The intermediate buffers of a call as views of ONE arena, sized from (B, n_max) and kept: a call of the same shape gets the
         same views, a larger one replaces the arena (after asking whether the device has the memory)."""
@@ -148,36 +126,24 @@ class CorpusFeatureExtractor:
 
     # ------------------------------------------------------------------ stages
     def _dft(self, w, x, out):
-        if self.dft_mode == "fp32":
-            # The arithmetic mode is a process-global of the library, read when a call is issued: switched for this call and put back
-            # (sv_frontend.TisvFrontEnd.dft).  Correct for one issuing thread; callers keep extraction on the thread that trains.
-            prev = _lib.lib().ssv_set_precision(0)
-            try:
-                self.voc._dft(w, x, out)
-            finally:
-                _lib.lib().ssv_set_precision(prev)
-        else:
+        with fp32_products() if self.dft_mode == "fp32" else contextlib.nullcontext():
             self.voc._dft(w, x, out)
         return out
 
     def _front(self, y, lengths, orig_sr, tick=lambda name: None):
         """Everything up to the maxima: returns (dims, views) with lin / mel / n_frames filled.  ``tick(name)`` is called after each stage
         has been issued (tools/bench_corpus_features.py synchronises there)."""
-        _check_wave(y, lengths, device=self.device)
+        check_wave(y, lengths, device=self.device)
         B, n_max = y.shape
         d = _dims(B, n_max, self.cfg, orig_sr)
         if d["resampled"]:
-            self._bank(orig_sr, upload=False)                               # an unsupported ratio raises before anything is allocated
+            self.resampler.bank(orig_sr, upload=False)                               # an unsupported ratio raises before anything is allocated
         v = self._views(d)
-        bank = self._bank(orig_sr) if d["resampled"] else None
         st, T = ops._stream(), d["T_max"]
         if d["resampled"]:
-            w, up, down, left, taps = bank
-            y_res = v["y_res"].view(B, d["m_max"])
-            _lib.call("ssv_resample_sinc", _p(y), _p(lengths), _p(w), _p(y_res), _p(v["n_res"]), B, n_max, d["m_max"], up, down, taps, left, st)
-            y, lengths = y_res, v["n_res"]
+            y, lengths = self.resampler.resample(y, lengths, orig_sr, out=v["y_res"].view(B, d["m_max"]), n_out=v["n_res"])
             tick("resample")
-        _lib.call("ssv_trim_bounds", _p(y), _p(lengths), _p(v["bounds"]), B, d["m_max"], TRIM_TOP_DB, 2048, 512, st)
+        trim_bounds(y, lengths, TRIM_TOP_DB, out=v["bounds"])
         tick("trim_bounds")
         fr = v["fr"].view(B, self.n_fft, T)
         _lib.call("ssv_preemph_frames_ragged", _p(y), _p(v["bounds"]), _p(fr), _p(v["n_frames"]), B, d["m_max"], self.n_fft, self.hop, T,
@@ -196,14 +162,16 @@ class CorpusFeatureExtractor:
             tick("rowmax x 2")
         return d, v
 
+    def _split(self, flat, B, RT, i32):
+        """The three views of a flat result [mel | lin | rt], a torch tensor or its numpy copy (``i32``: that library's int32)."""
+        n_mel, n_lin = B * self.M * RT, B * self.F * self.r * RT
+        return flat[:n_mel].reshape(B, self.M, RT), flat[n_mel:n_mel + n_lin].reshape(B, self.F, self.r * RT), flat[n_mel + n_lin:].view(i32)
+
     def _pack(self, d, v, RT):
         """One flat result tensor [mel | lin | rt] (so that a caller who wants the batch on the host copies once) and its three views."""
         B, r = d["B"], self.r
-        n_mel, n_lin = B * self.M * RT, B * self.F * r * RT
-        flat = torch.empty((n_mel + n_lin + B,), dtype=_F32, device=self.device)
-        mel = flat[:n_mel].view(B, self.M, RT)
-        lin = flat[n_mel:n_mel + n_lin].view(B, self.F, r * RT)
-        rt = flat[n_mel + n_lin:].view(_I32)
+        flat = torch.empty((B * (self.M * RT + self.F * r * RT + 1),), dtype=_F32, device=self.device)
+        mel, lin, rt = self._split(flat, B, RT, _I32)
         log = self.log_feature
         _lib.call("ssv_corpus_normalize_pack", _p(v["lin"]), _p(v["mel"]), None if log else _p(v["max_lin"]), None if log else _p(v["max_mel"]),
                   _p(v["n_frames"]), _p(mel), _p(lin), _p(rt), B, self.F, self.M, d["T_max"], RT, r, int(log), self.power, self.ref_db, self.max_db,
@@ -212,25 +180,18 @@ class CorpusFeatureExtractor:
 
     def resample(self, y, lengths, orig_sr):
         """The first stage alone: ((B, m_max) waveforms at SAMPLING_RATE, (B,) int32 lengths), fresh tensors (``metagen.py:29-62``)."""
-        _check_wave(y, lengths, device=self.device)
+        check_wave(y, lengths, device=self.device)
         if int(orig_sr) == self.sr:
             return y.clone(), lengths.clone()
-        w, up, down, left, taps = self._bank(orig_sr)
-        B, n_max = y.shape
-        m_max = int(np.ceil(n_max * (float(up) / float(down))))
-        out = torch.empty((B, m_max), dtype=_F32, device=y.device)
-        n_out = torch.empty((B,), dtype=_I32, device=y.device)
-        _lib.call("ssv_resample_sinc", _p(y), _p(lengths), _p(w), _p(out), _p(n_out), B, n_max, m_max, up, down, taps, left, ops._stream())
-        return out, n_out
+        return self.resampler.resample(y, lengths, orig_sr)
 
     def trim_bounds(self, y, lengths):
         """``librosa.effects.trim(speech, 22)`` bounds of rows already at SAMPLING_RATE: (B, 2) int32."""
-        from .sv_frontend import trim_bounds
         return trim_bounds(y, lengths, TRIM_TOP_DB)
 
     def frames(self, y, bounds):
         """``ssv_preemph_frames_ragged`` alone: ((B, n_fft, T_max) frames, (B,) int32 frame counts), T_max = 1 + n_max // hop."""
-        _check_wave(y, bounds, bounds=True, device=self.device)
+        check_wave(y, bounds, bounds=True, device=self.device)
         B, n_max = y.shape
         T = 1 + n_max // self.hop
         fr = torch.empty((B, self.n_fft, T), dtype=_F32, device=y.device)
@@ -252,10 +213,7 @@ class CorpusFeatureExtractor:
         """``__call__`` followed by ONE device-to-host copy of the whole result: numpy (mel, lin, rt)."""
         d, v = self._front(y, lengths, orig_sr)
         flat = self._pack(d, v, d["RT_max"])[0].cpu().numpy()
-        B, RT = d["B"], d["RT_max"]
-        n_mel, n_lin = B * self.M * RT, B * self.F * self.r * RT
-        return (flat[:n_mel].reshape(B, self.M, RT), flat[n_mel:n_mel + n_lin].reshape(B, self.F, self.r * RT),
-                flat[n_mel + n_lin:].view(np.int32))
+        return self._split(flat, d["B"], d["RT_max"], np.int32)
 
     def collated(self, y, lengths, orig_sr):
         """The batch as the collate functions pad it -- to its OWN longest item: (mel (B, M, w), lin (B, F, r * w), rt) with w = max(rt) (at

@@ -3,28 +3,23 @@
 // normalisation, the time reduction and the zero padding of the collated batch in one pass.  Waveforms are (B, n_max) float32 rows with
 // DEVICE (start, end) bounds each (ssv_trim_bounds); nothing below reads a length on the host and every shape is static.
 #include "ssv_common.h"
+#include "frame_stage.h"
 
 #define CF_THREADS 256
 #define CF_LDS_FLOATS 12800        // 51,200 bytes: three workgroups per CU
-// LDS image of a tile's staged sample range: sample s at s + (s >> sh), hop = 2^sh * q with q odd (sh = 31, no skew, for an odd hop).
-// Lane t of a wave reads sample t * hop + i, which lands at t * (hop + q) + i + (i >> sh): the lane stride hop + q is odd, so the 32
-// lanes of a ds_read_b32 group meet 32 different banks (hop = 256: stride 257; hop = 160: stride 165, the skew of dvector.hip).
-#define CF_SKEW(s, sh) ((s) + ((s) >> (sh)))
 
 // ---- librosa.effects.trim's segment, np.append(x[0], x[1:] - a * x[:-1]) and librosa.stft's framing (data/dataset.py:95-97) ----------
 // fr[b][i][t] = reflect_pad(p, N / 2)[t * hop + i] for t < T_b = 1 + len / hop, p the pre-emphasised seg = y[b][start:end] (p[0] =
 // seg[0]: the sample before `start` is not read), zeros for t >= T_b; a segment of len <= N / 2 has nothing to reflect from and gets
-// T_b = 0.  A workgroup owns `tile` frames of one row: it stages the pre-emphasised samples they read ONCE in LDS (coalesced, the
-// reflection applied on the way in; frames overlap by 1 - hop / N) and writes each of the N sample rows as one run of `tile` floats.
-// p is one fused multiply-add per sample, a single fp32 rounding; it never reaches memory.
+// T_b = 0.  A workgroup owns `tile` frames of one row: it stages the pre-emphasised samples they read once in LDS, skewed by sh = ctz(hop),
+// and writes each of the N sample rows as one run of `tile` floats (frame_stage.h).
 __global__ __launch_bounds__(CF_THREADS) void preemph_frames_ragged_kernel(const float* __restrict__ y, const int* __restrict__ bounds,
                                                                            float* __restrict__ fr, int* __restrict__ n_frames, int n_max, int N,
                                                                            int hop, int T_max, int tile, int tshift, int sh, float a) {
   __shared__ float sm[CF_LDS_FLOATS];
   const int b = blockIdx.y, t0 = blockIdx.x * tile;
   int start = bounds[2 * b], end = bounds[2 * b + 1];
-  start = start < 0 ? 0 : (start > n_max ? n_max : start);
-  end = end < start ? start : (end > n_max ? n_max : end);
+  ssv_clamp_span(start, end, n_max);
   const int len = end - start;
   int Tb = len > N / 2 ? 1 + len / hop : 0;
   if (Tb > T_max) Tb = T_max;                             // T_max >= 1 + n_max / hop (checked on the host): never taken
@@ -32,28 +27,16 @@ __global__ __launch_bounds__(CF_THREADS) void preemph_frames_ragged_kernel(const
   int cnt = Tb - t0;                                      // live frames of this tile (block-uniform)
   cnt = cnt < 0 ? 0 : (cnt > tile ? tile : cnt);
   if (cnt > 0) {
-    const float* seg = y + (long)b * n_max + start;
-    const int lo = t0 * hop - N / 2, count = (cnt - 1) * hop + N;   // CF_SKEW(count - 1) < CF_LDS_FLOATS, checked on the host
-    for (int s = threadIdx.x; s < count; s += CF_THREADS) {
-      int j = lo + s;
-      if (j < 0) j = -j;
-      else if (j >= len) j = 2 * (len - 1) - j;           // 0 <= j < len: len > N / 2 and the last frame starts at or before len
-      j = j < 0 ? 0 : (j >= len ? len - 1 : j);           // (kept in bounds whatever the caller's sizes)
-      const float x = seg[j];
-      sm[CF_SKEW(s, sh)] = j > 0 ? fmaf(-a, seg[j - 1], x) : x;
-    }
+    // ssv_skew(count - 1, sh) < CF_LDS_FLOATS, checked on the host
+    frame_stage_load<true, CF_THREADS>(sm, y + (long)b * n_max + start, len, t0 * hop - N / 2, (cnt - 1) * hop + N, sh, a);
     __syncthreads();
   }
   const int t = threadIdx.x & (tile - 1), col = t0 + t;
   if (col >= T_max) return;
   float* dst = fr + (long)b * N * T_max + col;
-  const int rows = CF_THREADS >> tshift, s0 = t * hop;
-  if (t < cnt) {
-#pragma unroll 4
-    for (int i = threadIdx.x >> tshift; i < N; i += rows) dst[(long)i * T_max] = sm[CF_SKEW(s0 + i, sh)];
-  } else {
-    for (int i = threadIdx.x >> tshift; i < N; i += rows) dst[(long)i * T_max] = 0.f;
-  }
+  const int rows = CF_THREADS >> tshift;
+  if (t < cnt) frame_stage_store(sm, dst, T_max, t * hop, threadIdx.x >> tshift, rows, N, sh);
+  else for (int i = threadIdx.x >> tshift; i < N; i += rows) dst[(long)i * T_max] = 0.f;
 }
 
 // ---- normalisation, time reduction and collate padding (data/dataset.py:101-118, :215-224) ------------------------------------------

@@ -5,22 +5,20 @@
 // checks every table entry it reads against the buffers' sizes and skips what does not fit, so a wrong table cannot write out of
 // bounds.  All sums run in a fixed order (no atomics).
 #include "ssv_common.h"
+#include "frame_stage.h"
 
 #define DV_THREADS 256
 #define DV_TILE 64                 // frames of one workgroup's tile: one 256-byte run per sample row and wave store
 #define DV_SPAN_MAX 12288          // floats of a tile's staged sample range, (DV_TILE - 1) * hop + n_fft; 10,592 at hop 160, n_fft 512
-// LDS image of the range: sample s at s + s / 32.  Lane t of a wave reads sample t * hop + i; at hop = 160 = 5 * 32 all 32 lanes of a
-// ds_read_b32 group would meet in ONE bank, with the skew lane t is in bank (5 t + i + i / 32) mod 32: conflict-free.  (Any hop = 32 q
-// with q odd is; other hops are merely correct.)
-#define DV_SKEW(s) ((s) + ((s) >> 5))
+#define DV_SKEW_SHIFT 5            // ssv_skew's shift: conflict-free at hop = 160 = 5 * 32
 #define DV_LDS_FLOATS (DV_SPAN_MAX + DV_SPAN_MAX / 32 + 1)      // 50,692 bytes: three workgroups per CU
 
 // ---- librosa.stft's framing (dvector_create.py:43) of every span, all frames ---------------------------------------------------------
 // tiles (n_tiles, 6) int: row, span start, span end, first frame f0 of the tile in its span, its first compact frame index g0, frame
 // count cnt <= DV_TILE.  Compact frame g of this call (g = g0 + t - g_base, 0 <= g < n_frames) is column g % Tc of item g / Tc:
 // fr[g / Tc][i][g % Tc] = reflect_pad(seg, N / 2)[(f0 + t) * hop + i], seg = y[row][start:end].  A workgroup stages the samples its
-// tile reads ONCE (coalesced, the reflection applied on the way in; frames overlap by 1 - hop / N) and writes each of the N sample rows as
-// one run of cnt floats.  Workgroup n_tiles zeroes the pad columns of the last item.
+// tile reads once in LDS and writes each of the N sample rows as one run of cnt floats (frame_stage.h).  Workgroup n_tiles zeroes the
+// pad columns of the last item.
 __global__ __launch_bounds__(DV_THREADS) void span_frames_kernel(const float* __restrict__ y, const int* __restrict__ tiles,
                                                                  float* __restrict__ fr, int B, int n_max, int n_tiles, int N, int hop,
                                                                  int Tc, int R, int g_base, int n_frames) {
@@ -38,22 +36,12 @@ __global__ __launch_bounds__(DV_THREADS) void span_frames_kernel(const float* __
   if (row < 0 || row >= B || start < 0 || end > n_max || len <= N / 2 || f0 < 0 || cnt < 1 || cnt > DV_TILE ||
       (long)(f0 + cnt - 1) * hop > (long)len)
     return;
-  const float* seg = y + (long)row * n_max + start;
-  const int lo = f0 * hop - N / 2, count = (cnt - 1) * hop + N;       // count <= DV_SPAN_MAX, checked on the host
-  for (int s = threadIdx.x; s < count; s += DV_THREADS) {
-    int j = lo + s;
-    if (j < 0) j = -j;
-    else if (j >= len) j = 2 * (len - 1) - j;               // 0 <= j < len: len > N / 2 and the last frame starts at or before len
-    sm[DV_SKEW(s)] = seg[j];
-  }
+  frame_stage_load<false, DV_THREADS>(sm, y + (long)row * n_max + start, len, f0 * hop - N / 2, (cnt - 1) * hop + N, DV_SKEW_SHIFT, 0.f);   // count <= DV_SPAN_MAX, checked on the host
   __syncthreads();
   const int wave = threadIdx.x >> 6, t = threadIdx.x & 63;
   const long g = (long)g0 + t - g_base;
   if (t >= cnt || g < 0 || g >= n_frames) return;
-  float* dst = fr + (g / Tc) * (long)N * Tc + g % Tc;
-  const int s0 = t * hop;
-#pragma unroll 4
-  for (int i = wave; i < N; i += DV_THREADS / 64) dst[(long)i * Tc] = sm[DV_SKEW(s0 + i)];
+  frame_stage_store(sm, fr + (g / Tc) * (long)N * Tc + g % Tc, Tc, t * hop, wave, DV_THREADS / 64, N, DV_SKEW_SHIFT);
 }
 
 // ---- S[:, j:j + 24] for j = 0, 12, ... (dvector_create.py:48-52) as rows of the frames-major log-mel array -----------------------------

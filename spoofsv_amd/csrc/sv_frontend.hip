@@ -5,6 +5,7 @@
 // Waveforms are (B, n_max) float32 rows with a DEVICE int length each; nothing below reads a length on the host, every shape is
 // static, so the whole chain replays from a captured graph.  All sums run in a fixed order (no atomics).
 #include "ssv_common.h"
+#include "frame_stage.h"
 
 #define SVF_THREADS 256
 #define SVF_SPAN_MAX 8192         // floats of one workgroup's staged input span (resampler)
@@ -86,15 +87,10 @@ __global__ __launch_bounds__(SVF_THREADS) void trim_bounds_kernel(const float* _
   for (int f = wave; f < nf; f += SVF_THREADS / 64) {
     float acc = 0.f;
     for (int c = lane; c < FL; c += 64) {
-      int j = f * hop + c - pad;
+      const int j = f * hop + c - pad;
       float v = 0.f;
-      if (reflect) {
-        if (j < 0) j = -j;
-        else if (j >= n) j = 2 * (n - 1) - j;
-        v = yb[j];
-      } else if (j >= 0 && j < n) {
-        v = yb[j];
-      }
+      if (reflect) v = yb[ssv_reflect(j, n)];
+      else if (j >= 0 && j < n) v = yb[j];
       acc = fmaf(v, v, acc);
     }
     acc = svf_wave_sum(acc);
@@ -146,8 +142,7 @@ __global__ __launch_bounds__(128) void tisv_frames_kernel(const float* __restric
                                                           int T, int min_len) {
   const int t = blockIdx.x * 128 + threadIdx.x, c = blockIdx.y, b = blockIdx.z >> 1, s = blockIdx.z & 1;
   int start = bounds[2 * b], end = bounds[2 * b + 1];
-  start = start < 0 ? 0 : (start > n_max ? n_max : start);
-  end = end < start ? start : (end > n_max ? n_max : end);
+  ssv_clamp_span(start, end, n_max);
   const int len = end - start;
   const bool ok = len > min_len;                        // min_len >= max(N / 2, T * hop): reflect padding and T frames exist
   if (blockIdx.x == 0 && c == 0 && s == 0 && threadIdx.x == 0) valid[b] = ok ? 1 : 0;
@@ -155,10 +150,7 @@ __global__ __launch_bounds__(128) void tisv_frames_kernel(const float* __restric
   float v = 0.f;
   if (ok) {
     const int f0 = s ? 1 + len / hop - T : 0;
-    int j = (f0 + t) * hop + c - N / 2;
-    if (j < 0) j = -j;
-    else if (j >= len) j = 2 * (len - 1) - j;
-    v = y[(long)b * n_max + start + j];
+    v = y[(long)b * n_max + start + ssv_reflect((f0 + t) * hop + c - N / 2, len)];
   }
   fr[((long)blockIdx.z * N + c) * T + t] = v;
 }
@@ -200,8 +192,7 @@ __global__ __launch_bounds__(SVF_THREADS) void segment_peak_kernel(const float* 
   __shared__ float red[SVF_THREADS];
   const int b = blockIdx.x;
   int start = bounds[2 * b], end = bounds[2 * b + 1];
-  start = start < 0 ? 0 : (start > n_max ? n_max : start);
-  end = end < start ? start : (end > n_max ? n_max : end);
+  ssv_clamp_span(start, end, n_max);
   const int len = min(end - start, clip);
   const float* yb = y + (long)b * n_max + start;
   float m = -INFINITY;

@@ -4,6 +4,7 @@
 // Spectra are (B, 2F, T) float32: rows [0, F) real parts, rows [F, 2F) imaginary parts, T frames (fastest).
 // Frame matrices are (B, N, T): row c = sample c of every frame, so they are the (B, C, T) operands of the 1x1 convs.
 #include "ssv_common.h"
+#include "frame_stage.h"
 
 // ---- Griffin-Lim phase step: a = reb - alpha * tprev;  proj = mag * a / (|a| + 1e-16) --------------------------------
 // librosa 0.7.0 core.griffinlim loop body (`angles[:] = rebuilt - momentum/(1+momentum)*tprev; angles /= abs(angles)+1e-16`)
@@ -50,9 +51,7 @@ __global__ __launch_bounds__(256) void ola_frames_kernel(const float* __restrict
   const int t = blockIdx.x * 256 + threadIdx.x, c = blockIdx.y;
   if (t >= T) return;
   const int len = hop * (T - 1);
-  int j = t * hop + c - N / 2;           // index into the trimmed waveform
-  if (j < 0) j = -j;
-  else if (j >= len) j = 2 * (len - 1) - j;
+  const int j = ssv_reflect(t * hop + c - N / 2, len);     // index into the trimmed waveform
   const long bo = (long)blockIdx.z * N * T;
   out[bo + (long)c * T + t] = ola_at(fr + bo, inv_env, j + N / 2, N, T, hop);
 }
@@ -69,10 +68,7 @@ __global__ __launch_bounds__(256) void ola_signal_kernel(const float* __restrict
 __global__ __launch_bounds__(256) void frame_signal_kernel(const float* __restrict__ y, float* __restrict__ fr, int n, int N, int T, int hop) {
   const int t = blockIdx.x * 256 + threadIdx.x, c = blockIdx.y;
   if (t >= T) return;
-  int j = t * hop + c - N / 2;
-  if (j < 0) j = -j;
-  else if (j >= n) j = 2 * (n - 1) - j;
-  fr[((long)blockIdx.z * N + c) * T + t] = y[(long)blockIdx.z * n + j];
+  fr[((long)blockIdx.z * N + c) * T + t] = y[(long)blockIdx.z * n + ssv_reflect(t * hop + c - N / 2, n)];
 }
 
 // ---- per-row max, (x / max)^p * s ------------------------------------------------------------------------------------

@@ -9,10 +9,14 @@ fp32 -> ``ssv_power_mel_log`` -> ``ssv_gather_windows`` -> ``SpeechEmbedder`` (`
 The first half of this file is host logic in plain integers and float64, importable without a device; every function names the
 reference lines it restates.  ``DvectorExtractor`` is the device pipeline.  There is no CPU fallback: a non-ROCm tensor raises.
 """
-import ctypes
 from types import SimpleNamespace
 
 import numpy as np
+import torch
+
+from . import _lib, ops
+from .ops import _p
+from .wave import check_wave
 
 TILE = 64          # frames of one ssv_span_frames tile (DV_TILE in csrc/dvector.hip: the kernel skips a longer one)
 
@@ -120,10 +124,6 @@ def plan(spans_per_utterance, hop, window=24, shift=12, lengths=None, tile=TILE)
 
 
 # ------------------------------------------------------------------------------------------------------------ device pipeline
-def _p(t):
-    return ctypes.c_void_p(t.data_ptr())
-
-
 class DvectorExtractor:
     """dvector_create.py:92-101 for a ragged batch on one device.  ``front_end``: a ``TisvFrontEnd`` (its rate, n_fft, hop, mel basis and
     Fourier basis are used; its ``tisv_frame`` is not), ``embedder``: a ``SpeechEmbedder`` on the same device.  ``window`` / ``shift``:
@@ -152,8 +152,7 @@ class DvectorExtractor:
     def plan(self, y16, lengths, spans=None):
         """``spans=None``: one span per utterance, its ``trim_bounds(..., 30)``.  That default reads the (B, 2) bounds to the host ONCE
         (and the lengths, to clip explicit spans) -- the plan's tables are built there."""
-        from .sv_frontend import _check_wave
-        _check_wave(y16, lengths, device=self.fe.device)
+        check_wave(y16, lengths, device=self.fe.device)
         if spans is None:
             b = self.fe.trim_bounds(y16, lengths, 30).cpu().tolist()
             spans = [[(s, e)] for s, e in b]
@@ -165,8 +164,6 @@ class DvectorExtractor:
     # ------------------------------------------------------------------ stages
     def span_frames(self, y16, tiles, g_base, n_frames, out=None):
         """Compact frames [g_base, g_base + n_frames) of the device tile table ``tiles`` -> (R, nfft, COLS), R = ceil(n_frames / COLS)."""
-        import torch
-        from . import _lib, ops
         fe, Tc = self.fe, self.COLS
         R = -(-n_frames // Tc)
         fr = out if out is not None else torch.empty((R, fe.nfft, Tc), dtype=torch.float32, device=y16.device)
@@ -177,8 +174,6 @@ class DvectorExtractor:
     def log_mel(self, y16, pl, timers=None):
         """All frames of the plan -> the compact frames-major log-mel array (ceil(n_frames / COLS) * COLS, nmels); rows past n_frames
         belong to zero frames."""
-        import torch
-        from . import _lib, ops
         fe, Tc, G = self.fe, self.COLS, pl.n_frames
         dev = y16.device
         mel = torch.empty((-(-G // Tc) * Tc, fe.nmels), dtype=torch.float32, device=dev)
@@ -195,21 +190,17 @@ class DvectorExtractor:
             tick("frames")
             S = fe.dft(fr)
             tick("dft")
-            R = fr.shape[0]
-            _lib.call("ssv_power_mel_log", _p(S), _p(fe.mel), ctypes.c_void_p(mel.data_ptr() + 4 * g_base * fe.nmels), R, fe.F, Tc, fe.nmels, 1e-6,
-                      ops._stream())
+            fe.mel_log(S, out=mel[g_base:g_base + fr.shape[0] * Tc])
             tick("mel")
         return mel
 
     def gather(self, mel, g0, lo, n, out):
         """Windows [lo, lo + n) of the device table ``g0`` into the first n rows of ``out`` (rows, window, nmels)."""
-        from . import _lib, ops
-        _lib.call("ssv_gather_windows", _p(mel), ctypes.c_void_p(g0.data_ptr() + 4 * lo), _p(out), mel.shape[0], n, self.window, self.fe.nmels,
+        _lib.call("ssv_gather_windows", _p(mel), _p(g0[lo:]), _p(out), mel.shape[0], n, self.window, self.fe.nmels,
                   ops._stream())
 
     def window_features(self, y16, lengths, spans=None, pl=None):
         """The (n_windows, window, nmels) windows themselves -- what the reference stacks at dvector_create.py:98-99 -- and the plan."""
-        import torch
         pl = pl or self.plan(y16, lengths, spans)
         out = torch.empty((pl.n_windows, self.window, self.fe.nmels), dtype=torch.float32, device=y16.device)
         if pl.n_windows:
@@ -218,7 +209,6 @@ class DvectorExtractor:
 
     def window_embeddings(self, y16, lengths, spans=None, pl=None, timers=None):
         """(n_windows, proj) embeddings of every window (eval mode, no_grad), and the plan."""
-        import torch
         pl = pl or self.plan(y16, lengths, spans)
         dev, W = y16.device, self.windows_per_call
         P = self.net.dims[3]
@@ -247,8 +237,6 @@ class DvectorExtractor:
         return E, pl
 
     def _means(self, E, offs, normalize):
-        import torch
-        from . import _lib, ops
         P = offs.shape[0] - 1
         out = torch.empty((P, E.shape[1]), dtype=torch.float32, device=E.device)
         if P > 0 and E.shape[0] > 0:

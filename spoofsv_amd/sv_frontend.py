@@ -12,73 +12,17 @@ for ``win_length < n_fft``.  It runs in exact fp32 (``dft_mode="fp32"``) by defa
 magnitudes, which magnifies the split modes' 2e-5-of-the-peak error in quiet bands, and the product is tiny.
 There is no CPU fallback: a non-ROCm tensor raises.
 """
-import ctypes
-from fractions import Fraction
+import contextlib
 
 import numpy as np
 import torch
 
 from . import _lib, ops
+from .ops import _p
 from .vocoder import _slaney_mel
+from .wave import KAISER_BEST, Resampler, check_wave, fp32_products, polyphase_bank, rocm_device, sinc_table, trim_bounds  # noqa: F401 (re-exported)
 
 _F32, _I32 = torch.float32, torch.int32
-
-# resampy's 'kaiser_best' filter as published with resampy (resampy/filters.py, data/kaiser_best.npz): a Kaiser-windowed sinc of 64 zero
-# crossings sampled 2^9 times per crossing
-KAISER_BEST = dict(num_zeros=64, precision=9, beta=14.769656459379492, rolloff=0.9475937167399596)
-_BANK_MAX = 1 << 20       # up * taps (ssv_resample_sinc)
-_SPAN_MAX = 8192
-
-
-def _p(t):
-    return ctypes.c_void_p(t.data_ptr())
-
-
-def sinc_table(num_zeros, precision, beta, rolloff):
-    """resampy.filters.sinc_window with a Kaiser window: the right half of the filter, num_zeros * 2^precision + 1 samples (float64)."""
-    n = (1 << precision) * num_zeros
-    sinc = rolloff * np.sinc(rolloff * np.linspace(0, num_zeros, num=n + 1, endpoint=True))
-    return np.kaiser(2 * n + 1, beta)[n:] * sinc
-
-
-def polyphase_bank(orig_sr, sr, filt=None):
-    """The (up, taps) float64 filter bank of ``resampy.resample(x, orig_sr, sr)`` for the rational ratio up / down = sr / orig_sr, and
-    ``left``: tap j of phase p weighs x[n - left + j] for the output at input time n + p / up.  resampy's inner loops (interpolation
-    between table entries, the ``min(1, ratio)`` stretch of the table index and of the gain) are evaluated once per phase here instead
-    of once per output sample there; entries its loops never reach are zero.  Returns (bank, up, down, left)."""
-    r = Fraction(int(sr), int(orig_sr))
-    up, down = r.numerator, r.denominator
-    f = dict(KAISER_BEST, **(filt or {}))
-    win = sinc_table(f["num_zeros"], f["precision"], f["beta"], f["rolloff"])
-    ratio = float(sr) / float(orig_sr)
-    num_table = 1 << f["precision"]
-    if ratio < 1:
-        win = win * ratio
-    delta = np.zeros_like(win)
-    delta[:-1] = np.diff(win)
-    scale = min(1.0, ratio)
-    step = int(scale * num_table)
-    nwin = win.shape[0]
-    reach = nwin // step + 1
-    if up * (2 * reach) > _BANK_MAX or 255 * down // up + 2 * reach + 2 > _SPAN_MAX:
-        raise ValueError("spoofsv_amd.sv_frontend: the ratio %d/%d (%d Hz -> %d Hz) needs a filter bank of %d x %d taps; unsupported"
-                         % (up, down, orig_sr, sr, up, 2 * reach))
-    left = reach - 1
-    bank = np.zeros((up, 2 * reach), dtype=np.float64)
-    for p in range(up):
-        frac = scale * (p / up)                                   # left wing: x[n - i]
-        idx = frac * num_table
-        off = int(idx)
-        eta = idx - off
-        i = np.arange((nwin - off) // step)
-        bank[p, left - i] = win[off + i * step] + eta * delta[off + i * step]
-        frac = scale - frac                                       # right wing: x[n + k + 1]
-        idx = frac * num_table
-        off = int(idx)
-        eta = idx - off
-        k = np.arange((nwin - off) // step)
-        bank[p, left + 1 + k] = win[off + k * step] + eta * delta[off + k * step]
-    return bank, up, down, left
 
 
 def stft_basis(n_fft, win_length):
@@ -94,30 +38,9 @@ def stft_basis(n_fft, win_length):
     return np.ascontiguousarray(fwd, dtype=np.float32)[:, :, None]
 
 
-def _check_wave(y, ints, bounds=False, device=None):
-    """``ints``: the rows' live lengths (B,), or with ``bounds`` their (start, end) pairs (B, 2); ``device``: where the caller's constants live."""
-    if not (torch.is_tensor(y) and y.is_cuda and y.dtype == _F32 and y.dim() == 2 and y.is_contiguous() and y.shape[0] > 0 and y.shape[1] > 0):
-        raise RuntimeError("spoofsv_amd.sv_frontend: waveforms must be a contiguous float32 ROCm tensor (B, n_max); no CPU fallback exists")
-    if device is not None and y.device != device:
-        raise RuntimeError("spoofsv_amd.sv_frontend: waveforms are on %s, this front end's bases and filter banks on %s" % (y.device, device))
-    want = (y.shape[0], 2) if bounds else (y.shape[0],)
-    if not (torch.is_tensor(ints) and ints.dtype == _I32 and ints.is_contiguous() and tuple(ints.shape) == want and ints.device == y.device):
-        raise RuntimeError("spoofsv_amd.sv_frontend: %s must be a contiguous int32 tensor %s on the waveforms' device, got %s"
-                           % ("bounds" if bounds else "lengths", want, (tuple(ints.shape), ints.dtype, ints.device) if torch.is_tensor(ints) else type(ints)))
-
-
-def trim_bounds(y, lengths, top_db=30.0, frame_length=2048, hop_length=512):
-    """``librosa.effects.trim(y, top_db)`` bounds of every row (the device form of ``vocoder.trim_silence``): (B, 2) int32 (start, end)."""
-    _check_wave(y, lengths)
-    B, n_max = y.shape
-    bounds = torch.empty((B, 2), dtype=_I32, device=y.device)
-    _lib.call("ssv_trim_bounds", _p(y), _p(lengths), _p(bounds), B, n_max, float(top_db), int(frame_length), int(hop_length), ops._stream())
-    return bounds
-
-
 def segment_peak(y, bounds, clip, peak=0.75):
     """generate_test_utterances.py:135-139 after the trim: (B, clip) rows y[start:end][:clip] / max * peak, zero-padded, and their lengths."""
-    _check_wave(y, bounds, bounds=True)
+    check_wave(y, bounds, bounds=True)
     B, n_max = y.shape
     out = torch.empty((B, int(clip)), dtype=_F32, device=y.device)
     n = torch.empty((B,), dtype=_I32, device=y.device)
@@ -130,11 +53,7 @@ class TisvFrontEnd:
     arithmetic mode in force, split-fp16 unless changed)."""
 
     def __init__(self, sr=16000, nfft=512, window=0.025, hop=0.01, nmels=40, tisv_frame=120, device="cuda", dft_mode="fp32"):
-        dev = torch.device(device)
-        if dev.type != "cuda":
-            raise RuntimeError("spoofsv_amd.sv_frontend: needs a ROCm device (no CPU fallback exists), got %s" % dev)
-        if dev.index is None:
-            dev = torch.device("cuda", torch.cuda.current_device())
+        dev = rocm_device(device, "sv_frontend")
         if dft_mode not in ("fp32", "default"):
             raise ValueError("dft_mode must be 'fp32' or 'default'")
         self.sr, self.nfft, self.nmels, self.tisv_frame, self.device, self.dft_mode = int(sr), int(nfft), int(nmels), int(tisv_frame), dev, dft_mode
@@ -146,7 +65,7 @@ class TisvFrontEnd:
         self.F = self.nfft // 2 + 1
         self.w_fwd = torch.from_numpy(stft_basis(self.nfft, self.win_length)).to(dev)
         self.mel = torch.from_numpy(np.ascontiguousarray(_slaney_mel(self.sr, self.nfft, self.nmels))).to(dev)
-        self._banks = {}
+        self.resampler = Resampler(self.sr, dev)
 
     @classmethod
     def from_config(cls, ge2e_cfg, device=None, **kw):
@@ -156,36 +75,17 @@ class TisvFrontEnd:
         return cls(sr=d["sr"], nfft=d["nfft"], window=d["window"], hop=d["hop"], nmels=d["nmels"], tisv_frame=d["tisv_frame"], device=dev, **kw)
 
     # ------------------------------------------------------------------ stages
-    def _bank(self, orig_sr):
-        key = (int(orig_sr), self.sr)
-        b = self._banks.get(key)
-        if b is None:
-            if key[0] == key[1]:
-                b = (None, 1, 1, 0, 0)
-            else:
-                bank, up, down, left = polyphase_bank(key[0], key[1])
-                b = (torch.from_numpy(np.ascontiguousarray(bank, dtype=np.float32)).to(self.device), up, down, left, bank.shape[1])
-            self._banks[key] = b
-        return b
-
     def resample(self, y, lengths, orig_sr):
         """``librosa.load(path, sr)``'s resampling of every row: ((B, m_max) waveforms at ``sr``, (B,) int32 lengths)."""
-        _check_wave(y, lengths, device=self.device)
-        bank, up, down, left, taps = self._bank(orig_sr)
-        B, n_max = y.shape
-        m_max = int(np.ceil(n_max * (float(up) / float(down))))
-        out = torch.empty((B, m_max), dtype=_F32, device=y.device)
-        n_out = torch.empty((B,), dtype=_I32, device=y.device)
-        _lib.call("ssv_resample_sinc", _p(y), _p(lengths), _p(bank) if bank is not None else None, _p(out), _p(n_out), B, n_max, m_max, up, down,
-                  taps, left, ops._stream())
-        return out, n_out
+        check_wave(y, lengths, device=self.device)
+        return self.resampler.resample(y, lengths, orig_sr)
 
     def trim_bounds(self, y, lengths, top_db=30):
         return trim_bounds(y, lengths, top_db)
 
     def frames(self, y, bounds):
         """((2B, nfft, tisv_frame) frames of the first / last slices, (B,) int32 valid flags)."""
-        _check_wave(y, bounds, bounds=True, device=self.device)
+        check_wave(y, bounds, bounds=True, device=self.device)
         B, n_max = y.shape
         fr = torch.empty((2 * B, self.nfft, self.tisv_frame), dtype=_F32, device=y.device)
         valid = torch.empty((B,), dtype=_I32, device=y.device)
@@ -197,22 +97,17 @@ class TisvFrontEnd:
         """(R, nfft, T) frames -> (R, 2F, T) spectra through the library's 1x1 convolution."""
         R, _, T = fr.shape
         S = torch.empty((R, 2 * self.F, T), dtype=_F32, device=fr.device)
-        if self.dft_mode == "fp32":
-            # The arithmetic mode is a process-global of the library (ssv_set_precision), read when a call is issued: it is switched for
-            # this one call and put back.  Correct for one issuing thread, and under capture (the kernel is chosen at capture time);
-            # another thread that issues library calls inside this window would run them in fp32 as well.
-            prev = _lib.lib().ssv_set_precision(0)
-            try:
-                ops._conv_fwd(fr, self.nfft * T, self.w_fwd, None, None, S, 2 * self.F * T, 1, 1, 0)
-            finally:
-                _lib.lib().ssv_set_precision(prev)
-        else:
+        with fp32_products() if self.dft_mode == "fp32" else contextlib.nullcontext():
             ops._conv_fwd(fr, self.nfft * T, self.w_fwd, None, None, S, 2 * self.F * T, 1, 1, 0)
         return S
 
-    def mel_log(self, S):
+    def mel_log(self, S, out=None):
+        """(R, 2F, T) spectra -> (R, T, nmels) log-mel frames; into ``out``, R * T * nmels contiguous floats, when given."""
         R, _, T = S.shape
-        out = torch.empty((R, T, self.nmels), dtype=_F32, device=S.device)
+        if out is None:
+            out = torch.empty((R, T, self.nmels), dtype=_F32, device=S.device)
+        elif not (out.dtype == _F32 and out.device == S.device and out.is_contiguous() and out.numel() == R * T * self.nmels):
+            raise RuntimeError("spoofsv_amd.sv_frontend: mel_log's out must hold %d x %d x %d contiguous float32 on %s" % (R, T, self.nmels, S.device))
         _lib.call("ssv_power_mel_log", _p(S), _p(self.mel), _p(out), R, self.F, T, self.nmels, 1e-6, ops._stream())
         return out
 

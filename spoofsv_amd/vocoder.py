@@ -19,12 +19,12 @@ The basis entries carry 16 mantissa bits (bf16 hi + lo), so one transform is acc
 (librosa's complex64 FFT: ~1e-7); Griffin-Lim's own spectral inconsistency is 1e-1..1e-2, four orders above that.
 There is no CPU fallback: tensors must be on a ROCm device.
 """
-import ctypes
 
 import numpy as np
 import torch
 
 from . import _lib, ops, resident
+from .ops import _p
 
 _F32 = torch.float32
 
@@ -91,10 +91,6 @@ def trim_silence(y, top_db=60.0, frame_length=2048, hop_length=512):
         return y[0:0], (0, 0)
     start, end = int(nz[0]) * hop_length, min(len(y), (int(nz[-1]) + 1) * hop_length)
     return y[start:end], (start, end)
-
-
-def _p(t):
-    return ctypes.c_void_p(t.data_ptr())
 
 
 class Vocoder:

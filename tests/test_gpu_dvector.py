@@ -144,6 +144,56 @@ def test_span_frames_bitwise_against_the_restatement():
     assert np.array_equal(p[:, :G - 256], flat[:, 256:G]) and not p[:, G - 256:].any()
 
 
+def test_the_framers_agree_with_each_other():
+    """ssv_span_frames, ssv_preemph_frames_ragged at preemph = 0.0 (fmaf(-0.0, p, x) == x for every finite p), ssv_frame_signal on the
+    contiguous slice and _sv_frontend_ref.frames cast to float32 are copies of the same samples: equal bit for bit on the live frames,
+    the ragged entry exactly zero past T_b, the span entry exactly zero in its pad columns.  At hop 160 and 128 the skew shift is 5 on
+    the span path and ctz(hop) = 5 / 7 on the ragged one; both take a 64-frame tile at both hops.  Spans: inside one tile from the row's
+    first sample; one frame past a tile boundary, interior at both ends; ending at the row's last sample."""
+    from spoofsv_amd import _lib, ops
+    from spoofsv_amd import dvector as D
+    from spoofsv_amd.dvector import DvectorExtractor
+    from spoofsv_amd.sv_frontend import TisvFrontEnd
+    from spoofsv_amd.vocoder import Vocoder
+    n = 24000
+    rng = np.random.default_rng(61)
+    rows = [speechlike(rng, n, 0, 0) for _ in range(3)]
+    y, _ = _batch(rows)
+    assert tuple(y.shape) == (3, n)
+    net = _embedder()
+    for hop in (160, 128):
+        spans = [(0, 30 * hop + 7), (777, 777 + 128 * hop), (n - 70 * hop - 3, n)]
+        ref = [R.frames(rows[b][s:e], NFFT, hop).astype(np.float32) for b, (s, e) in enumerate(spans)]
+        assert [r.shape for r in ref] == [(NFFT, 31), (NFFT, 129), (NFFT, 71)]
+        fe = TisvFrontEnd(hop=hop / 16000.0, device=DEV)
+        assert (fe.nfft, fe.hop_length) == (NFFT, hop)
+        ex = DvectorExtractor(fe, net)
+        pl = D.plan([[s] for s in spans], hop, WIN, 12, lengths=[n] * 3)
+        G = pl.n_frames
+        assert G == 231 and [t[5] for t in pl.tiles.tolist()] == [31, 64, 64, 1, 64, 7]
+        fr = torch.full((1, NFFT, ex.COLS), float("nan"), device=DEV)
+        ex.span_frames(y, torch.from_numpy(pl.tiles).to(DEV), 0, G, out=fr)
+        span = fr[0].cpu().numpy()
+        assert not span[:, G:].any(), hop                                # the pad columns: exactly zero (and no NaN is left)
+        T = 1 + n // hop
+        bounds = torch.tensor(spans, dtype=torch.int32, device=DEV)
+        rag = torch.full((3, NFFT, T), float("nan"), device=DEV)
+        nf = torch.full((3,), -1, dtype=torch.int32, device=DEV)
+        _lib.call("ssv_preemph_frames_ragged", ops._p(y), ops._p(bounds), ops._p(rag), ops._p(nf), 3, n, NFFT, hop, T, 0.0, ops._stream())
+        assert nf.cpu().tolist() == [31, 129, 71]
+        rag = rag.cpu().numpy()
+        voc = Vocoder(NFFT, hop, DEV)
+        g = 0
+        for b, (s, e) in enumerate(spans):
+            F = ref[b].shape[1]
+            assert np.array_equal(span[:, g:g + F], ref[b]), (hop, b, "span_frames")
+            assert np.array_equal(rag[b, :, :F], ref[b]), (hop, b, "preemph_frames_ragged")
+            assert not rag[b, :, F:].any(), (hop, b)                     # past T_b: exactly zero
+            assert np.array_equal(voc.frames(y[b:b + 1, s:e].contiguous())[0].cpu().numpy(), ref[b]), (hop, b, "frame_signal")
+            g += F
+        assert g == G
+
+
 def test_all_frame_log_mel_vs_restatement():
     """Every frame of every span: mel POWER within mel_basis . (2 |S| d + d^2), d = 2e-5 max|S| -- the bar test_gpu_sv_frontend.py holds
     the two slices to.  Then ssv_gather_windows, bitwise against numpy slicing of the device's own log-mel array."""
