@@ -102,7 +102,9 @@ int ssv_conv1d_bwd_weight(const float* dy, long dy_bs, const float* dy_amax, int
 int ssv_rowsum(const float* x, long x_bs, float* out, int B, int C, int L, ssv_stream_t stream);
 /* out(c) = sum_{b,t} x(b,c,t): the bias gradient of a conv layer in one launch (ABI 7; ssv_rowsum + ssv_sum_slabs before), fixed summation order. */
 int ssv_bias_grad(const float* x, long x_bs, float* out, int B, int C, int L, ssv_stream_t stream);
-/* out[i] = sum_{z<Z} slabs[z*stride + i], i < n, summed in index order (bitwise reproducible). */
+/* out[i] = sum_{z<Z} slabs[z*stride + i], i < n.  The order is fixed, so the result is bitwise reproducible, but it is NOT index order: four
+ * accumulators a_u take slabs u, u + 4, u + 8, ... of the first 4 * (Z / 4) slabs in increasing z, the remaining Z % 4 slabs are then added
+ * to a_0 in increasing z, and out[i] = (a_0 + a_1) + (a_2 + a_3). */
 int ssv_sum_slabs(const float* slabs, float* out, long n, int Z, long stride, ssv_stream_t stream);
 /* dst(b, 0:n) = src(b, 0:n) for B rows with independent row strides (the Q half of torch.cat((R, Q), 1),
  * models/TTSModel.py:270). */
