@@ -20,16 +20,18 @@ typedef __attribute__((ext_vector_type(4))) float f32x4;
 // with X(b,c,col) = 0 outside 0 <= col < Lx.  Used for: dilated/causal Conv1d forward,
 // its data gradient (transposed weights, negated shifts), 1x1 convs, the two halves of
 // ConvTranspose1d(k=2,s=2), attention V*A / K*dS / K^T*Q and the LSTM projections.
+// (The three argument structs carry their defaults -- "not used" for every optional part, unit column strides, one tap, one batch item --
+// so a caller names only what its product has; they stay trivially copyable: they are kernel arguments.)
 struct GemmNN {
-  const float* A; long sab, sam, sac, saj;
-  const float* X; long sxb, sxc, sxn; int Lx;
-  float* C; long scb, scm, scn;
-  const float* bias;
-  const float* bias_b; long sbb;
-  const float* R; long srb, srm, srn;
-  int M, N, Kc, KT, B;
-  int shift[3];
-  float alpha;               // scales the accumulated product only (attention 1/sqrt(d))
+  const float* A = nullptr; long sab = 0, sam = 0, sac = 0, saj = 0;
+  const float* X = nullptr; long sxb = 0, sxc = 0, sxn = 1; int Lx = 0;
+  float* C = nullptr; long scb = 0, scm = 0, scn = 1;
+  const float* bias = nullptr;
+  const float* bias_b = nullptr; long sbb = 0;
+  const float* R = nullptr; long srb = 0, srm = 0, srn = 1;
+  int M = 0, N = 0, Kc = 0, KT = 1, B = 1;
+  int shift[3] = {0, 0, 0};
+  float alpha = 1.f;         // scales the accumulated product only (attention 1/sqrt(d))
 };
 int ssv_launch_gemm_nn(const GemmNN& g, hipStream_t st);
 
@@ -38,87 +40,87 @@ int ssv_launch_gemm_nn(const GemmNN& g, hipStream_t st);
 // Used for: Conv1d weight gradient (split over batches into slabs), ConvTranspose1d
 // weight gradient, attention dV = dR*A^T and dK = Q*dS^T (one output per batch).
 struct GemmNT {
-  const float* A; long sab, sam, sat; int La;
-  const float* X; long sxb, sxc, sxn; int Lx;
-  float* C; long scz, scm, scc, scj;
-  int M, Nc, KT, B, Z, bstep;   // bstep > 0: slab z reduces over batch items z, z + bstep, ...; bstep == 0 (gemm_nt_bf3's extra-row kernel): over the z-th of Z equal chunk ranges
-  int shift[3];
+  const float* A = nullptr; long sab = 0, sam = 0, sat = 1; int La = 0;
+  const float* X = nullptr; long sxb = 0, sxc = 0, sxn = 1; int Lx = 0;
+  float* C = nullptr; long scz = 0, scm = 0, scc = 1, scj = 0;
+  int M = 0, Nc = 0, KT = 1, B = 1, Z = 1, bstep = 1;   // bstep > 0: slab z reduces over batch items z, z + bstep, ...; bstep == 0 (gemm_nt_bf3's extra-row kernel): over the z-th of Z equal chunk ranges
+  int shift[3] = {0, 0, 0};
   // several problems of one shape in one launch (split-bf16 kernel only): grid.z = njobs * Z, entry z belongs to job z / Z and
   // takes A = jobs[job].dy, X = jobs[job].x, the job's shifts, and slab (z % Z) of the job's slab region C + job * Z * scz
-  const ssv_wgrad_job* jobs; int njobs;
-  int max_shift;           // with a job table: the caller's bound on |shift| over all jobs (picks the k = 3 ring kernel when <= 64); < 0 = unknown
+  const ssv_wgrad_job* jobs = nullptr; int njobs = 0;
+  int max_shift = -1;      // with a job table: the caller's bound on |shift| over all jobs (picks the k = 3 ring kernel when <= 64); < 0 = unknown
   // split-fp16 arithmetic (split-bf16 kernel only): both operands are scaled while they are split, by the power of two that
   // the maximum over ALL entries of their partial-maxima lists gives (the reduction runs over the batch, so one scale per
   // tensor); with a job table the lists are the job's (dy_amax / x_amax, n_amax entries each side as stored in the job).
-  int f16; const float* a_amax; int a_namax; const float* x_amax; int x_namax;
+  int f16 = 0; const float* a_amax = nullptr; int a_namax = 0; const float* x_amax = nullptr; int x_namax = 0;
 };
 int ssv_launch_gemm_nt(const GemmNT& g, hipStream_t st);
 
 // ---- split-MFMA variants (conv_nn.hip, wgrad_nt.hip, wgrad_nt3r.hip, pwln.hip; helpers in bf3_common.h): same contracts, unit column strides, weights pre-split --------------
 struct GemmNNB {
-  const unsigned short* Ahi; const unsigned short* Alo; int Kpad;   // bf16 planes (hi, lo) in fragment order, see pack_split_kernel
-  const float* X; long sxb, sxc; int Lx;
-  float* C; long scb, scm;
-  const float* bias;
-  const float* bias_b; long sbb;
-  const float* R; long srb, srm;
-  int M, N, Kc, KT, B;
-  int shift[3];
-  int sxn, scn;            // column strides of X and C (1 everywhere except the stride-2 deconvolution halves; R needs scn == 1)
+  const unsigned short* Ahi = nullptr; const unsigned short* Alo = nullptr; int Kpad = 0;   // bf16 planes (hi, lo) in fragment order, see pack_split_kernel
+  const float* X = nullptr; long sxb = 0, sxc = 0; int Lx = 0;
+  float* C = nullptr; long scb = 0, scm = 0;
+  const float* bias = nullptr;
+  const float* bias_b = nullptr; long sbb = 0;
+  const float* R = nullptr; long srb = 0, srm = 0;
+  int M = 0, N = 0, Kc = 0, KT = 1, B = 1;
+  int shift[3] = {0, 0, 0};
+  int sxn = 1, scn = 1;    // column strides of X and C (1 everywhere except the stride-2 deconvolution halves; R needs scn == 1)
   // row_pair = 1 (round 6; the transposed convolution's forward in ONE product over 2 Cout rows): output row m, column n goes to
   // C(b, m >> 1, 2 n + (m & 1)) -- scm is the stride of those M / 2 rows of 2 N floats -- and bias is indexed by m >> 1.  Plain k = 1 products only
   // (M even, scn == 1, no R / LSTM / statistics).  c_amax != null: the launch also leaves the output's operand-scale list, c_namax entries per
   // item at c_amax + b * c_namax: entry = the workgroup's tile (max |C| over it), the entries past the tiles zeroed by the item's last tile.
-  int row_pair; float* c_amax; int c_namax;
+  int row_pair = 0; float* c_amax = nullptr; int c_namax = 0;
   // LSTM wavefront at inference with PRE-SPLIT recurrent activations (round 6; hs_planes != null, split-fp16 mode, lstm_D == 2): |h| < 1, so its
   // operand scale is the constant 2^14 and the cell epilogue can write h already split -- fp16 hi / lo planes in the consumer's own staging order,
   // [k-group of 8 units][column][8 halves] over hs_npad columns (a multiple of the column tile; the pad columns stay zero) -- for (layer, ring slot) at
   // hs_planes + ((layer * 2 + slot) * 2 + {0: hi, 1: lo}) * hs_plane_bytes.  The products then stage their input with 16-byte loads and no VALU split.
-  unsigned short* hs_planes; long hs_plane_bytes; int hs_npad;
-  int hs_keep_h;            // (with hs_planes) 1: this launch also stores the fp32 h -- only the wavefront's last step needs it, for the caller's h_last
+  unsigned short* hs_planes = nullptr; long hs_plane_bytes = 0; int hs_npad = 0;
+  int hs_keep_h = 1;        // (with hs_planes) 1: this launch also stores the fp32 h -- only the wavefront's last step needs it, for the caller's h_last
   // ksplit > 1 (round 6; plain k = 1 products whose K is long and whose output is small -- the LSTM backward's [W_ih | W_hh]^T dgates): grid.y = B * ksplit,
   // entry (b, z) reduces over input rows [z Kc, (z + 1) Kc) against weight chunks [z Kc / 32, ...) of planes whose row length is Kpad = ksplit * Kc and
   // writes its partial product at C + b scb + z scz (the consumer adds the slabs).  skip_rows: entry b = 0 has no use for its row tiles below this row.
-  int ksplit; long scz; int skip_rows;
+  int ksplit = 1; long scz = 0; int skip_rows = 0;
   // x0_planes (with hs_planes, layer 0 riding along): layer 0's input frames pre-split as the recurrent activations are -- frame t at x0_planes + t * 2 *
   // hs_plane_bytes, the first 4 * xsplit0 k-groups of the hi and of the lo plane, split with the frames' own power-of-two scale (x0_amax: 64 partial maxima) --
   // so that W_ih x_t is the FIRST K segment (xsplit0 chunks, an even number) of layer 0's product instead of a projection of all frames written to memory
   // and read back through R: A0hi / A0lo are then the planes of [W_ih | W_hh] (K = 32 xsplit0 + H).  The accumulators are rescaled by 2^14 / (the frames'
   // scale) between the segments, exactly (powers of two): h's scale is the constant 2^14.
-  const unsigned short* x0_planes; const float* x0_amax; int xsplit0;
+  const unsigned short* x0_planes = nullptr; const float* x0_amax = nullptr; int xsplit0 = 0;
   // LSTM support.  perm_h = H > 0: output row m is gate (m % 4) of hidden unit (m / 4), i.e. row (m % 4) * H + m / 4 of
   // the torch layout -- the weights were packed in that order and the bias vectors are indexed through the same map.
   // epi = 1: fused cell epilogue -- the 4 accumulator rows of a lane are the (i, f, g, o) pre-activations of one unit;
   // the kernel adds R (the input projection) and the biases, updates cstate [H][N] in place and writes h to C [H][N].
-  int perm_h, epi, first;
-  float* cstate;
+  int perm_h = 0, epi = 0, first = 0;
+  float* cstate = nullptr;
   // LSTM wavefront (epi == 1 with lstm_D > 0): grid.y entry b is layer lstm_lo + b at frame t = lstm_s - layer.  The K axis
   // has two segments: chunks [0, xsplit) read the lower layer's h_t, chunks [xsplit, Kpad/32) the layer's own h_{t-1}
   // (skipped at t = 0).  All h live in lstm_out[layer][slot = frame % lstm_D][H][N]; the kernel derives X, X2 and C from
   // (layer, t), and offsets the weight planes by b*sab, the biases by b*sbb and cstate by layer*H*N.
-  float* lstm_out; int lstm_s, lstm_lo, lstm_D, xsplit; long sab;
+  float* lstm_out = nullptr; int lstm_s = 0, lstm_lo = 0, lstm_D = 0, xsplit = 0; long sab = 0;
   // Layer 0 in the same launch (round 5; A0hi != null, lstm_lo == 0): entry 0 is layer 0 at frame lstm_s -- its K axis is the layer's own
   // h_{t-1} alone (xsplit chunks of the planes A0hi / A0lo; none at t = 0), its input projection comes in through R (no batch stride), and
   // the entries b >= 1 are layers 1 .. with planes Ahi + (b - 1) * sab.  One launch per wavefront step instead of two.
-  const unsigned short* A0hi; const unsigned short* A0lo;
+  const unsigned short* A0hi = nullptr; const unsigned short* A0lo = nullptr;
   // training (gates_out != null, lstm_D = number of frames): the activated gates i, f, g, o are saved as
   // gates_out[layer][frame][gate*H + u][N] (torch row order) and cstate is [layer][frame][H][N] (c_{t-1} read, c_t written)
-  float* gates_out;
+  float* gates_out = nullptr;
   // split-fp16 arithmetic (f16 = 1, see "split-fp16" below; with the LSTM epilogue one weight scale serves all layers of a launch and
   // the activations, |h| < 1, take the fixed scale 2^14 from a one-entry list holding 1.0): the planes hold fp16
   // hi / lo of A * 2^ea and *a_inv = 2^-ea (written by the pack kernels); X is scaled by 2^ex while it is split, with ex from
   // the maximum of the x_namax partial maxima |X| at x_amax + b * x_amax_bs (x_amax_bs = 0: one list for every batch item).
-  int f16; const float* a_inv; const float* x_amax; int x_namax; long x_amax_bs;
+  int f16 = 0; const float* a_inv = nullptr; const float* x_amax = nullptr; int x_namax = 0; long x_amax_bs = 0;
   // Column statistics of the OUTPUT for the LayerNorm that follows (highwayConv: the reduction over channels runs across the
   // GEMM's M axis, i.e. across workgroups; this makes the LayerNorm / gate forward a reduction-free streaming kernel):
   // colstats[((b * (M / 64) + m / 64) * N + n) * 2 + {0, 1}] = mean and sum of squared deviations of C(b, 64-row group, n)
   // over the group's 64 rows, bias included.  Needs M % 64 == 0, unit column stride, no LSTM epilogue.  Null: not wanted.
-  float* colstats;
+  float* colstats = nullptr;
   // One output row beyond the last full 128-row tile, kept out of the MFMA tiles (gemm_nn_bf3w_kernel<.., XR = 1>, k = 1): M = 128 j + 1 output
   // rows -- the 513-channel layers of SSRN -- cost a whole extra row tile of MFMAs for ONE row otherwise.  xrow_w[k * xrow_sk], k < Kc, is that
   // row of the fp32 weight; the kernel launches over M - 1 rows and the workgroups of row tile 0 add the row as plain fp32 dot products
   // from the values they stage anyway.  Null: not used.
-  const float* xrow_w; long xrow_sk;
+  const float* xrow_w = nullptr; long xrow_sk = 0;
 };
 int ssv_launch_gemm_nn_bf3(const GemmNNB& g, hipStream_t st);
 // 1x1 product (g: KT = 1, unit strides, no residual / LSTM epilogue, M <= 640) that finishes LayerNorm over its M rows and the activation in
@@ -158,9 +160,6 @@ int ssv_launch_absmax(const float* x, long x_bs, int B, long n, float* out, int 
 int ssv_nt_bf3_tiles(int KT, int M, int Nc);
 void ssv_nt_bf3_tile(int KT, int M, int Nc, int* wm, int* ntc);
 int ssv_nt_bf3_wg_per_cu(int KT, int wm, int ntc);        // co-resident workgroups per CU of that instantiation (its register count)
-// layout of a weight's resident planes (api.hip): bytes of ONE plane (the lo plane follows the hi plane), and where 2^-ea is kept (split-fp16)
-size_t ssv_split_bytes(int rows, int K, int k);
-const float* ssv_packed_inv(const void* w_packed, int Cout, int Cin, int k, int transposed);
 int ssv_precision();      // 0 = exact fp32 MFMA, 1 = split-bf16 MFMA, 2 = split-fp16 MFMA with power-of-two operand scales (default)
 // The three tuning knobs that remain (per-shape overrides for in-step sweeps: SSV_NNB_FORCE="kt:M:N=wm,nt;...", SSV_NT_FORCE="M:Nc:k=Z;...",
 // SSV_LN_GROUPS for tools/bench_ln.py): read from the environment ONCE at first use -- a launch must not cost getenv() scans -- and

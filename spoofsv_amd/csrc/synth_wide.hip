@@ -11,6 +11,7 @@
 // split-fp16: the operand scale is the power of two of the workgroup's own tile (its 32 columns of all segments, scanned once before
 // the product), so no scale lists travel between the layers and an item's rounding depends only on the items of its 32-column tile.
 #include "bf3_common.h"
+#include "ssv_host.h"
 
 #define WD_BN 32                      // columns per workgroup
 #define WD_LDT (WD_BN + 1)            // row pitch of the fp32 pre-activation tile in LDS
@@ -261,9 +262,8 @@ static int wide_weights(WideArgs& a, const float* w, const void* w_packed, int M
   a.Ahi = a.Alo = nullptr; a.a_inv = nullptr;
   if (ssv_precision() == 0) return 0;
   SSV_CHECK(w_packed, SSV_BAD_SHAPE, "%s: the split-MFMA modes read the weight's resident planes (w_packed is null)", what);
-  a.Ahi = (const unsigned short*)w_packed;
-  a.Alo = (const unsigned short*)((const char*)w_packed + ssv_split_bytes(M, Cin, k));
-  a.a_inv = ssv_packed_inv(w_packed, M, Cin, k, 0);
+  const SplitPlanes pl = packed_planes(w_packed, M, Cin, k).fwd;
+  a.Ahi = pl.hi; a.Alo = pl.lo; a.a_inv = pl.inv;
   return 0;
 }
 

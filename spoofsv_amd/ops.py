@@ -529,7 +529,7 @@ class Conv1dFn(torch.autograd.Function):
 # operand has its list computed ONCE (``_dd_amax``: the producer's tag or one ssv_absmax launch) and handed to every product that
 # reads it -- x serves the forward and the weight gradient, dy both gradients -- instead of one fallback launch per product.
 def _tiny_conv(cin, cout):
-    """Mirrors SSV_MIN_SPLIT_CHANNELS of csrc/api.hip: a convolution with fewer than 32 input or output channels runs all three of its
+    """Mirrors SSV_MIN_SPLIT_CHANNELS of csrc/ssv_host.h: a convolution with fewer than 32 input or output channels runs all three of its
     products on the exact-fp32 kernels, which read no scale lists."""
     return min(int(cin), int(cout)) < 32
 

@@ -149,3 +149,22 @@ def test_conv_pack_plan_is_host_only_and_consistent():
     firsts = [jobs[i].first_block for i in range(2 * n)]
     assert firsts == sorted(firsts) and firsts[0] == 0 and firsts[-1] < nblocks
     assert L.ssv_conv_pack_plan(1, w, pl, co, ci, (ctypes.c_int * 1)(2), jobs) < 0      # kernel size 2 is not a conv weight here
+
+
+def test_host_queries_match_the_committed_answers():
+    """Every workspace size, slab count, partial-row count and the pack plan of tools/dump_host_queries.py, in the default arithmetic
+    mode, against tests/golden/host_queries.json: callers allocate by these answers and the entry points carve by the same layout
+    functions, so a size or a plan moves only by a deliberate edit of the fixture (regenerate it with the tool, --precision 2)."""
+    import importlib.util
+    import json
+    root = os.path.dirname(os.path.dirname(os.path.abspath(_lib.HEADER)))
+    spec = importlib.util.spec_from_file_location("dump_host_queries", os.path.join(root, "tools", "dump_host_queries.py"))
+    tool = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(tool)
+    got = tool.collect((2,))
+    want = json.load(open(os.path.join(root, "tests", "golden", "host_queries.json")))
+    assert sorted(got) == sorted(want) == ["2"]
+    for q in sorted(want["2"]):
+        assert got["2"].get(q) == want["2"][q], q
+    assert sorted(got["2"]) == sorted(want["2"])
+    assert tool.render(got) == open(os.path.join(root, "tests", "golden", "host_queries.json")).read()

@@ -1,6 +1,6 @@
 """GE2E training on the HIP path against a float64 run of the oracle, in every arithmetic mode.
 
-The LSTM backward (csrc/api.hip ssv_lstm_bwd: the reverse wavefront's merged data-gradient products, the cell backward, the weight gradients
+The LSTM backward (csrc/api_lstm_train.hip ssv_lstm_bwd: the reverse wavefront's merged data-gradient products, the cell backward, the weight gradients
 over all frames) and the GE2E loss kernels (csrc/lstm.hip) are compared per tensor with ``oracle/ge2e_oracle.py`` run in float64 on the
 GPU, at the embedder's real width (hidden 768, projection 256) and at the shapes where the kernels change form.  Each case runs the three
 modes back to back against the same float64 result:

@@ -679,7 +679,7 @@ def test_ge2e_backward_edge_shapes_vs_oracle(layers, T, precision):
 def test_ge2e_training_has_no_shape_limits(hidden, proj, B, T, layers, precision):
     """nn.LSTM + autograd (GE2E/speech_embedder_net.py:19, GE2E/train_speech_embedder.py:82-86) train at any hidden size and batch.  The
     wavefront training kernels need hidden % 32 == 0 and at least 8 utterances; every other shape -- and the whole exact-fp32 mode -- runs the
-    same iteration on the exact-fp32 GEMMs (csrc/api.hip lstm_train_fwd_f32): embeddings and every parameter gradient against autograd over
+    same iteration on the exact-fp32 GEMMs (csrc/api_lstm_train.hip lstm_train_fwd_f32): embeddings and every parameter gradient against autograd over
     the CPU oracle, in all three arithmetic modes."""
     from spoofsv_amd.ge2e import SpeechEmbedder
     torch.manual_seed(hidden + B)

@@ -185,7 +185,7 @@ def test_shared_texts_equal_the_expanded_batch(precision):
     """shared_texts = U with S speakers gives the (Y, A) of the expanded (S * U, 1, N) batch: bit-identical in the fp32 mode, within
     2e-4 in the split modes -- an item's operand scale (split-fp16) is that of its 32-column tile, so its values depend on its
     neighbours to rounding, and equality there is to rounding only.  U * N = 136 >= 128 on purpose: the text encoder's convolutions
-    take the exact-fp32 kernels below 128 columns in all (csrc/api.hip, use_bf3), so with fewer characters the U shared texts and the
+    take the exact-fp32 kernels below 128 columns in all (csrc/ssv_host.h, use_bf3), so with fewer characters the U shared texts and the
     S * U expanded ones would be ENCODED in two different arithmetics, which is not what this test is about."""
     from spoofsv_amd import synth
     with _mode(precision):
