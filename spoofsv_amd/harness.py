@@ -452,8 +452,9 @@ def ordinary_train(train_step, train_pattern, cfg, spec_dir=None, resume_checkpo
     than every bucket run eagerly.  Without it every iteration runs eagerly.  ``bucket_stats``: a dict that receives the bucketed step's
     counters (replays, eager, captures, capture_seconds, pool_bytes) when the run ends."""
     buckets = cfg.get("LENGTH_BUCKETS")
+    kind = train.step_kind(train_step)
     if buckets is not None:
-        train.check_buckets("text2mel" if train_step == "train_text2mel" else "ssrn", buckets, cfg["MAX_TEXT_LEN"], cfg["MAX_FRAME_NUM"])
+        train.check_buckets(kind, buckets, cfg["MAX_TEXT_LEN"], cfg["MAX_FRAME_NUM"])
     rank, world = _distributed(cfg)
     print = _rank0_print(rank)                               # the reference prints from its one process: rank 0 here
     dev = _device()
@@ -483,8 +484,7 @@ def ordinary_train(train_step, train_pattern, cfg, spec_dir=None, resume_checkpo
     bucketed = None
     if buckets is not None:
         opt.capturable = True                                # the step count lives on the device (replayed Adam)
-        bucketed = train.BucketedTrainStep("text2mel" if train_step == "train_text2mel" else "ssrn", model, opt, buckets,
-                                           gaw=gaw if train_step == "train_text2mel" else None, ddp=ddp, batch_size=cfg["BATCH_SIZE"])
+        bucketed = train.BucketedTrainStep(kind, model, opt, buckets, gaw=gaw, ddp=ddp, batch_size=cfg["BATCH_SIZE"])
     src = Prefetcher(BatchSource(cfg, train_step, cfg["BATCH_SIZE"], spec_dir, rank=rank, world=world, pattern=train_pattern), dev)
     val_src = BatchSource(cfg, train_step, 8, spec_dir, seed=7919, pattern=train_pattern, mode="validate")     # batch 8, :200
     if val_src.corpus is None:
@@ -496,15 +496,11 @@ def ordinary_train(train_step, train_pattern, cfg, spec_dir=None, resume_checkpo
             for i, sp in enumerate(src):
                 t0 = time.time()
                 sp = _pad_to_global(sp, world)
-                mel_gt = sp["data_0"].to(dev)
+                batch = [sp[k].to(dev) for k in train.KINDS[kind].keys]
                 if bucketed is not None:
-                    keys = ("data_1", "data_2") if train_step == "train_text2mel" else ("data_1",)
-                    terms = tuple(bucketed(mel_gt, *[sp[k].to(dev) for k in keys]))
-                elif train_step == "train_text2mel":
-                    l1, bd, la, att = train.text2mel_step(model, opt, mel_gt, sp["data_1"].to(dev), sp["data_2"].to(dev), gaw, ddp=ddp)
-                    terms = (l1, bd, la)
-                else:
-                    terms = train.ssrn_step(model, opt, mel_gt, sp["data_1"].to(dev), ddp=ddp)
+                    terms = tuple(bucketed(*batch))
+                else:                                                # (what train.text2mel_step / train.ssrn_step run)
+                    terms = tuple(train.TrainStep(kind, model, opt, batch, gaw, ddp, graph=False)())
                 if ddp is not None:
                     terms = ddp.all_reduce_mean(*terms)          # the log shows the global-batch loss, as the reference's gathered outputs do
                 terms = tuple(float(t.detach()) for t in terms)
@@ -556,6 +552,7 @@ def adversarial_train(train_step, train_pattern, cfg, spec_dir=None, resume_chec
     epoch = iteration = 0
     logs = {"wd_log": [], "loss_train_log_syn": [], "loss_train_log_syn_onlyfromD": [], "loss_train_log_disc": [], "loss_val_log": []}
     stepped = world > 1 or bool(cfg.get("CAPTURE_GRAPHS"))
+    kind = train.KINDS[train.step_kind(train_step)]
     ck = None
     if resume_checkpoints is None:
         model.apply(train.init_weights)
@@ -591,13 +588,7 @@ def adversarial_train(train_step, train_pattern, cfg, spec_dir=None, resume_chec
             opt_syn.zero_grad(set_to_none=True)
             opt_disc.zero_grad(set_to_none=True)
             target = "D" if iteration % (cfg["RATIO"] + 1) else "G"
-            mel_gt = sp["data_0"].to(dev)
-            if train_step == "train_text2mel":
-                gt = mel_gt
-                pred, att = model(train.shift_right(mel_gt), sp["data_1"].to(dev), sp["data_2"].to(dev))
-            else:
-                gt = sp["data_1"].to(dev)
-                pred, att = model(mel_gt), None
+            pred, att, gt = kind.forward(model, [sp[k].to(dev) for k in kind.keys])
             B, C, T = gt.shape
             if target == "G":
                 disc_syn = disc(pred)
@@ -659,35 +650,16 @@ def _adversarial_validate_and_save(train_step, cfg, model, disc, opt_syn, opt_di
     _save(os.path.join(save_dir, "{}_iteration_{}.tar.pth".format(train_step[6:], iteration + 1)), payload)
 
 
-def _restore_adam(opt, saved):
-    """Put a FusedAdam whose state tensors are baked into captured hipGraphs back to ``saved`` (a torch-style optimizer state
-    dict, or None = a fresh optimizer) by writing INTO the existing tensors."""
-    params = [p for g in opt.param_groups for p in g["params"]]
-    step = 0
-    for i, p in enumerate(params):
-        st = opt.state.get(p)
-        if not st:
-            continue
-        if saved is None:
-            st["exp_avg"].zero_(); st["exp_avg_sq"].zero_()
-        else:
-            sv = saved["state"][i]
-            st["exp_avg"].copy_(sv["exp_avg"]); st["exp_avg_sq"].copy_(sv["exp_avg_sq"])
-            step = int(sv["step"])
-    opt._steps = step
-    if opt._step_dev is not None:
-        opt._step_dev.fill_(step)
-
-
-def _adversarial_train_stepped(train_step, cfg, dev, model, disc, src, gaw, save_dir, logs, max_iter, val_src, ck, epoch, iteration,
-                               rank, world):
-    """adversarial_train on ``train.AdversarialGraphStep``: both iteration kinds replayed from hipGraphs when the batch shapes
-    are fixed (config key CAPTURE_GRAPHS with the synthetic source), run phase by phase otherwise; data parallel when
-    ``world`` > 1.  Same schedule, losses, logs and checkpoints as the eager loop."""
-    print = _rank0_print(rank)
+def _adversarial_setup(train_step, cfg, dev, model, disc, src, gaw, ck, rank, world):
+    """The capturable optimizers (at the checkpoint ``ck``'s state when resuming), the ``train.AdversarialGraphStep`` over the source's
+    batch shapes, and ``pick`` (collated batch -> the step's batch).  Capturing runs warm-up iterations: weights and optimizer state
+    are put back afterwards, written into the tensors the graphs hold (``train.TrainingSnapshot``)."""
     a = cfg["ADAM"]
     opt_syn = train.FusedAdam(model.parameters(), a["ALPHA"], (a["BETA_1"], a["BETA_2"]), a["EPSILON"], capturable=True)
     opt_disc = train.FusedAdam(disc.parameters(), a["ALPHA"], (a["BETA_1"], a["BETA_2"]), a["EPSILON"], capturable=True)
+    if ck is not None:          # before the capture: the graphs then hold the loaded moment tensors, and the snapshot is the checkpoint
+        opt_syn.load_state_dict(ck["opt_state_dict_syn"])
+        opt_disc.load_state_dict(ck["opt_state_dict_disc"])
     ddp_syn = ddp_disc = None
     if world > 1:
         ddp_syn = train.DataParallelRanks(model=model)
@@ -700,28 +672,26 @@ def _adversarial_train_stepped(train_step, cfg, dev, model, disc, src, gaw, save
         # mask per sample of the global batch (models/discriminator.py:27-36).  Must precede the capture: the seed is frozen in it.
         torch.cuda.manual_seed(int(cfg.get("SEED", 0)) + 7919 * (rank + 1))
     graph = bool(cfg.get("CAPTURE_GRAPHS")) and not src.source.files and src.source.corpus is None
-    w_model = {k: v.detach().clone() for k, v in model.state_dict().items()}
-    w_disc = {k: v.detach().clone() for k, v in disc.state_dict().items()}
-    kind = "text2mel" if train_step == "train_text2mel" else "ssrn"
+    kind = train.step_kind(train_step)
 
     def pick(sp):
         sp = _pad_to_global(sp, world)
-        keys = ("data_0", "data_1", "data_2") if kind == "text2mel" else ("data_0", "data_1")
-        return [sp[k].to(dev) for k in keys]
+        return [sp[k].to(dev) for k in train.KINDS[kind].keys]
     first = pick(next(iter(src.source)))          # shapes only; the prefetching iterator starts with the training loop
+    snapshot = train.TrainingSnapshot([model, disc], [opt_syn, opt_disc]).take()
     stepper = train.AdversarialGraphStep(kind, model, disc, opt_syn, opt_disc, first, gaw, cfg["LAMBDA"], ddp_syn, ddp_disc, graph=graph,
                                          coeff_seed=cfg.get("SEED", 0))
-    # capturing ran warm-up iterations: put weights and optimizer state back to the start of training (or to the checkpoint),
-    # writing into the tensors the graphs hold, and re-split the resident weight planes the captured convolutions read
-    model.load_state_dict(w_model)
-    disc.load_state_dict(w_disc)
-    _restore_adam(opt_syn, ck["opt_state_dict_syn"] if ck is not None else None)
-    _restore_adam(opt_disc, ck["opt_state_dict_disc"] if ck is not None else None)
-    if ck is not None and not opt_syn.state:      # nothing ran yet (eager phases): plain load
-        opt_syn.load_state_dict(ck["opt_state_dict_syn"])
-        opt_disc.load_state_dict(ck["opt_state_dict_disc"])
-    opt_syn.refresh_resident_weights()
-    opt_disc.refresh_resident_weights()
+    snapshot.restore()
+    return stepper, opt_syn, opt_disc, pick
+
+
+def _adversarial_train_stepped(train_step, cfg, dev, model, disc, src, gaw, save_dir, logs, max_iter, val_src, ck, epoch, iteration,
+                               rank, world):
+    """adversarial_train on ``train.AdversarialGraphStep``: both iteration kinds replayed from hipGraphs when the batch shapes
+    are fixed (config key CAPTURE_GRAPHS with the synthetic source), run phase by phase otherwise; data parallel when
+    ``world`` > 1.  Same schedule, losses, logs and checkpoints as the eager loop."""
+    print = _rank0_print(rank)
+    stepper, opt_syn, opt_disc, pick = _adversarial_setup(train_step, cfg, dev, model, disc, src, gaw, ck, rank, world)
     while epoch < cfg["MAX_EPOCHS"]:
         for sp in src:
             t0 = time.time()

@@ -14,6 +14,7 @@ import ctypes
 import os
 import contextlib
 import gc
+from types import SimpleNamespace
 
 import numpy as np
 import torch
@@ -187,6 +188,44 @@ class FusedAdam(torch.optim.Optimizer):
         self._key = None                      # moment tensors were replaced: rebuild the chunk table
 
 
+class TrainingSnapshot:
+    """Undo for the warm-up iterations of a capture, which train: ``take()`` clones every parameter and buffer of ``modules`` and, for
+    every FusedAdam of ``optimizers``, the moments and the true step count; ``restore()`` writes all of it back INTO THE SAME tensors
+    (captured hipGraphs hold their addresses) and re-splits the resident weight planes.
+    (The critics' dropout call counter, which the warm-up advances too, is not part of it.)"""
+
+    def __init__(self, modules, optimizers):
+        self.modules, self.optimizers = list(modules), list(optimizers)
+
+    def _tensors(self):
+        return [t for m in self.modules for t in list(m.parameters()) + list(m.buffers())]
+
+    def take(self):
+        self.weights = [t.detach().clone() for t in self._tensors()]
+        self.moments = [{p: (st["exp_avg"].clone(), st["exp_avg_sq"].clone()) for p, st in o.state.items() if "exp_avg" in st}
+                        for o in self.optimizers]
+        # the true step count: replays advance only the device counter, so the host's is stale once any graph has run
+        self.steps = [int(o._step_dev.item()) if o._step_dev is not None else o._steps for o in self.optimizers]
+        return self
+
+    @torch.no_grad()
+    def restore(self):
+        tensors = self._tensors()
+        for t, w in zip(tensors, self.weights):
+            t.copy_(w)
+        for o, saved, steps in zip(self.optimizers, self.moments, self.steps):
+            for p, st in o.state.items():
+                if "exp_avg" in st:
+                    for key, s in zip(("exp_avg", "exp_avg_sq"), saved.get(p, (None, None))):
+                        st[key].zero_() if s is None else st[key].copy_(s)       # (no saved moment: the state is the warm-up's)
+            o._steps = steps
+            if o._step_dev is not None:
+                o._step_dev.fill_(steps)
+            o.refresh_resident_weights()          # (the copies above bumped the weights' versions: the planes are re-split in place)
+        if tensors and tensors[0].is_cuda:
+            torch.cuda.synchronize()
+
+
 # --------------------------------------------------------------------------------------------- data
 def synthetic_text2mel_batch(B, N=186, T=325, freq_bins=80, spk_dim=200, vocab=34, seed=0, device=None):
     """VCTK-shaped synthetic batch: mel in (0,1), ids in [2, vocab) ending in
@@ -217,6 +256,43 @@ def shift_right(mel_gt):
     if mel_gt.is_cuda:          # one HIP launch that also leaves the result's operand scale list (ops.shift_right)
         return ops.shift_right(mel_gt)
     return torch.cat((torch.zeros_like(mel_gt[:, :, :1]), mel_gt[:, :, :-1]), dim=-1)          # host tensors (the tests' oracle inputs)
+
+
+# --------------------------------------------------------------------------------------------- step kinds
+# What the trainers need to know about a step kind, "text2mel" (batch = mel, text, spk) or "ssrn" (batch = mel, lin):
+#   keys                         the collated batch's entries, in batch order
+#   forward(model, batch)        -> (pred, att or None, target): the teacher-forced training forward
+#   need(batch)                  the batch's own maxima, what a length bucket must hold: (N_b, T_b) / (T_b,)
+#   static_shapes(bucket, batch) the shapes of the batch padded to ``bucket``
+#   spec_live, att_live          (index, mult) of ``ops.Live`` for the spectrogram losses / the attention loss of a masked step
+def _t2m_forward(model, batch):
+    mel, text, spk = batch
+    pred, att = model(shift_right(mel), text, spk)
+    return pred, att, mel
+
+
+def _ssrn_need(batch):
+    mel, lin = batch
+    if lin.shape[-1] != 4 * mel.shape[-1]:
+        raise ValueError("BucketedTrainStep: SSRN target has %d frames for %d mel frames (want 4x)" % (lin.shape[-1], mel.shape[-1]))
+    return (int(mel.shape[-1]),)
+
+
+KINDS = {
+    "text2mel": SimpleNamespace(
+        keys=("data_0", "data_1", "data_2"), forward=_t2m_forward, spec_live=(1,), att_live=(0,),
+        need=lambda batch: (int(batch[1].shape[-1]), int(batch[0].shape[-1])),
+        static_shapes=lambda bucket, batch: [tuple(batch[0].shape[:2]) + (bucket[1],), tuple(batch[1].shape[:2]) + (bucket[0],), tuple(batch[2].shape)]),
+    "ssrn": SimpleNamespace(
+        keys=("data_0", "data_1"), forward=lambda model, batch: (model(batch[0]), None, batch[1]), spec_live=(0, 4), att_live=None,
+        need=_ssrn_need,
+        static_shapes=lambda bucket, batch: [tuple(batch[0].shape[:2]) + (bucket[0],), tuple(batch[1].shape[:2]) + (4 * bucket[0],)]),
+}
+
+
+def step_kind(train_step):
+    """The kind of a harness step name ("train_text2mel" / "train_ssrn")."""
+    return "text2mel" if train_step == "train_text2mel" else "ssrn"
 
 
 # --------------------------------------------------------------------------------------------- DDP
@@ -493,6 +569,34 @@ def backward_segments(cuts, roots, side_roots=None, ddp=None, defer=None):
     return segs
 
 
+def segmented_exchange_phases(cuts, ddp, segment):
+    """The data-parallel tail of a backward whose segment 0 ran in the phase before: per segment of ``tts.ddp_plan`` a graph phase
+    ``segment(i)`` (i > 0), then an eager phase that starts bucket i's all-reduce; the last one also drains them all."""
+    phases, nseg = [], len(cuts.groups) + 1
+    for i in range(nseg):
+        if i > 0:
+            phases.append(("graph", lambda i=i: segment(i)))
+        last = i == nseg - 1
+        phases.append(("eager", (lambda i=i: (ddp.start_bucket(i), ddp.finish())) if last else (lambda i=i: ddp.start_bucket(i))))
+    return phases
+
+
+def warm_up(steppers, rounds):
+    """``rounds`` eager iterations of every ``PhasedStep`` in turn, before a capture.  They run on a side stream and the capture on
+    torch's capture stream: the parameters' AccumulateGrad nodes are created on the first and used on the second, which autograd
+    reports on every backward call.  Intended here."""
+    if hasattr(torch.autograd.graph, "set_warn_on_accumulate_grad_stream_mismatch"):
+        torch.autograd.graph.set_warn_on_accumulate_grad_stream_mismatch(False)
+    s = torch.cuda.Stream()
+    s.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(s):
+        for _ in range(rounds):
+            for st in steppers:
+                st._eager()
+    torch.cuda.current_stream().wait_stream(s)
+    torch.cuda.synchronize()
+
+
 class PhasedStep:
     """A training iteration as a list of phases ``(kind, fn)``: ``"graph"`` phases are device work only (kernel launches
     through libssv_hip / torch) and are captured into hipGraphs -- consecutive ones into one graph, all graphs sharing one
@@ -504,6 +608,7 @@ class PhasedStep:
         self.phases = phases
         self.use_graph = graph
         self.plan = None
+        self._graphs = []
         self.warmup = warmup
         self.drain = drain        # called after every eager phase WHILE CAPTURING: waits for the collectives it started
 
@@ -512,19 +617,20 @@ class PhasedStep:
             fn()
 
     def prepare(self):
+        """Warm up and capture (``graph=True``; a prepared step ignores further calls)."""
         if not self.use_graph or self.plan is not None:
             return self
-        # The warm-up runs on a side stream and the capture on torch's capture stream: the parameters' AccumulateGrad nodes
-        # are created on the first and used on the second, which autograd reports on every backward call.  Intended here.
-        if hasattr(torch.autograd.graph, "set_warn_on_accumulate_grad_stream_mismatch"):
-            torch.autograd.graph.set_warn_on_accumulate_grad_stream_mismatch(False)
-        s = torch.cuda.Stream()
-        s.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(s):
-            for _ in range(self.warmup):
-                self._eager()
-        torch.cuda.current_stream().wait_stream(s)
+        warm_up([self], self.warmup)
+        return self.capture()
+
+    def release(self):
+        """Drop the captured hipGraphs (nothing may be replaying them); the phases run eagerly until the next ``prepare()``."""
         torch.cuda.synchronize()
+        self.plan = None
+        self._graphs = []
+
+    def capture(self):
+        """Capture the (warmed-up) phases: ``plan`` = the replays and eager calls of one iteration, in order."""
         pool = self.pool = torch.cuda.graph_pool_handle()
         plan, i = [], 0
         while i < len(self.phases):
@@ -549,7 +655,7 @@ class PhasedStep:
                 for _, f in self.phases[i:j]:
                     f()
             plan.append(g.replay)
-            self._graphs = getattr(self, "_graphs", []) + [g]
+            self._graphs.append(g)
             i = j
         self.plan = plan
         return self
@@ -577,14 +683,19 @@ class TrainStep:
     segments of ``tts.ddp_plan`` and every gradient bucket's all-reduce is started right after its segment, overlapping the
     remaining segments; Adam follows the last collective.  ``out`` holds the iteration's loss terms (device scalars)."""
 
-    def __init__(self, kind, model, opt, batch=None, gaw=None, ddp=None, graph=False, defer_wgrad=False, lens=None):
+    def __init__(self, kind, model, opt, batch=None, gaw=None, ddp=None, graph=False, defer_wgrad=False, lens=None, static=None):
         self.kind, self.model, self.opt, self.gaw, self.ddp = kind, model, opt, gaw, ddp
         # lens: int32 device tensor of the batch's own maxima -- (N_b, T_b) for Text2Mel, (T_b,) for SSRN -- when the batch is padded to a
         # larger shape (BucketedTrainStep): the step then computes what the unpadded batch would (tts.live_lengths)
         self.lens = lens
+        self._lens_host = torch.empty(lens.numel(), dtype=torch.int32).pin_memory() if lens is not None else None     # see set_live_lengths
+        self._lens_copied = None
         # weight gradients of equal-shaped layers batched into one launch per backward segment (ops.DeferredWgrad)
         self.defer = ops.DeferredWgrad() if defer_wgrad else None
-        self.static = [b.clone() for b in batch] if (graph and batch is not None) else None
+        # static: the buffers a captured step reads -- given ones are adopted as they are, else the batch is cloned
+        if static is None and graph and batch is not None:
+            static = [b.clone() for b in batch]
+        self.static = static
         self.batch = self.static if self.static is not None else batch
         self.out = self.att = self.pred = None          # loss terms, attention and prediction of the last iteration (detached)
         self._seeds = {}              # (entries, value, device) -> constant gradient vector that seeds the backward
@@ -597,14 +708,9 @@ class TrainStep:
                              "only works with graph=False")
         self.cuts = Cuts(ddp.cut_names if seg else [])
         self._segs = None
-        nseg = len(self.cuts.groups) + 1
         phases = [("graph", self._forward_seg0)]
         if seg:
-            for i in range(nseg):
-                if i > 0:
-                    phases.append(("graph", lambda i=i: self._segs[i]()))
-                last = i == nseg - 1
-                phases.append(("eager", (lambda i=i: (ddp.start_bucket(i), ddp.finish())) if last else (lambda i=i: ddp.start_bucket(i))))
+            phases += segmented_exchange_phases(self.cuts, ddp, lambda i: self._segs[i]())
         elif ddp is not None:
             phases.append(("eager", ddp.all_reduce_grads))
         phases.append(("graph", self._adam))
@@ -632,27 +738,22 @@ class TrainStep:
             return (v, seedvec(v.numel(), v))
         masked = self.lens is not None
         live = (lambda: tts.live_lengths(self.model, self.lens)) if masked else contextlib.nullcontext
-        if self.kind == "text2mel":
-            mel, text, spk = self.batch
-            with _cuts_installed(self.model, self.cuts), live():
-                pred, att = self.model(shift_right(mel), text, spk)
-            lv = ops.spec_losses_vec(pred, mel, seedvec(2, pred), ops.Live(self.lens, 1) if masked else None)
-            av = ops.guided_att_loss_vec(att, self.gaw, ops.Live(self.lens, 0) if masked else None)
-            lvd, avd = lv.detach(), av.detach()
-            self.out, self.att, self.pred = (lvd[0], lvd[1], avd[0]), att.detach(), pred.detach()
+        kind = KINDS[self.kind]
+        with _cuts_installed(self.model, self.cuts), live():
+            pred, att, target = kind.forward(self.model, self.batch)
+        # (the seed is known: the loss's forward and backward share one pass)
+        lv = ops.spec_losses_vec(pred, target, seedvec(2, pred), ops.Live(self.lens, *kind.spec_live) if masked else None)
+        lvd = lv.detach()
+        self.out, self.pred = (lvd[0], lvd[1]), pred.detach()
+        roots, side_roots = [seed(lv)], None
+        if att is not None:
+            av = ops.guided_att_loss_vec(att, self.gaw, ops.Live(self.lens, *kind.att_live) if masked else None)
+            self.out, self.att = self.out + (av.detach()[0],), att.detach()
             if "dec_in" in self.cuts.rec:
-                segs = backward_segments(self.cuts, [seed(lv)], {"dec_in": [seed(av)]}, self.ddp, self.defer)
+                side_roots = {"dec_in": [seed(av)]}
             else:
-                segs = backward_segments(self.cuts, [seed(lv), seed(av)], None, self.ddp, self.defer)
-        else:
-            mel, lin = self.batch
-            with _cuts_installed(self.model, self.cuts), live():
-                pred = self.model(mel)
-            lv = ops.spec_losses_vec(pred, lin, seedvec(2, pred), ops.Live(self.lens, 0, 4) if masked else None)   # (the seed is known: the loss's forward and backward share one pass)
-            lvd = lv.detach()
-            self.out, self.pred = (lvd[0], lvd[1]), pred.detach()
-            segs = backward_segments(self.cuts, [seed(lv)], None, self.ddp, self.defer)
-        self._segs = segs
+                roots.append(seed(av))
+        segs = self._segs = backward_segments(self.cuts, roots, side_roots, self.ddp, self.defer)
         if self.loss_log is not None and not torch.cuda.is_current_stream_capturing():
             self.loss_log.append(torch.stack([o.reshape(()) for o in self.out]).clone())
         segs[0]()
@@ -671,12 +772,20 @@ class TrainStep:
     def release(self):
         """Drop the captured hipGraphs (nothing may be replaying them) and free the batched weight gradients' frozen job tables for the
         next ``prepare()``.  The step runs eagerly until then."""
-        torch.cuda.synchronize()
-        self.stepper.plan = None
-        self.stepper._graphs = []
+        self.stepper.release()
         if self.defer is not None:
             self.defer.release_capture()
         return self
+
+    def set_live_lengths(self, need):
+        """Write the batch's own maxima ``need`` into ``lens`` (through a pinned staging buffer, asynchronously) for the next iteration."""
+        if self._lens_copied is not None:
+            self._lens_copied.synchronize()       # the previous asynchronous copy out of the pinned buffer has run (long since, as a rule)
+        for j, v in enumerate(need):
+            self._lens_host[j] = v
+        self.lens.copy_(self._lens_host, non_blocking=True)
+        self._lens_copied = torch.cuda.Event()
+        self._lens_copied.record()
 
     def __call__(self, *batch):
         """Run one iteration; with a batch argument, on that batch (copied into the static buffers of a captured step)."""
@@ -795,24 +904,7 @@ class BucketedTrainStep:
             self.ddp.close()
 
     def _need(self, batch):
-        if self.kind == "text2mel":
-            mel, text, _ = batch
-            return (int(text.shape[-1]), int(mel.shape[-1]))
-        mel, lin = batch
-        if lin.shape[-1] != 4 * mel.shape[-1]:
-            raise ValueError("BucketedTrainStep: SSRN target has %d frames for %d mel frames (want 4x)" % (lin.shape[-1], mel.shape[-1]))
-        return (int(mel.shape[-1]),)
-
-    def _static(self, bucket, batch):
-        if self.kind == "text2mel":
-            N, T = bucket
-            mel, text, spk = batch
-            shapes = [(mel.shape[0], mel.shape[1], T), (text.shape[0], text.shape[1], N), tuple(spk.shape)]
-        else:
-            (T,) = bucket
-            mel, lin = batch
-            shapes = [(mel.shape[0], mel.shape[1], T), (lin.shape[0], lin.shape[1], 4 * T)]
-        return [torch.zeros(s, dtype=b.dtype, device=b.device) for s, b in zip(shapes, batch)]
+        return KINDS[self.kind].need(batch)
 
     def _capture(self, bucket, batch):
         import time
@@ -820,43 +912,21 @@ class BucketedTrainStep:
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         lens = torch.tensor(bucket, dtype=torch.int32, device=dev)
-        static = self._static(bucket, batch)
+        static = [torch.zeros(s, dtype=b.dtype, device=b.device) for s, b in zip(KINDS[self.kind].static_shapes(bucket, batch), batch)]
         for d, b in zip(static, batch):
             _pad_into(d, b)
-        # the capture's warm-up iterations train: keep weights and optimizer state, and put them back (into the same tensors) afterwards
-        saved_w = [p.detach().clone() for p in self.model.parameters()]
-        saved_opt = {id(p): (st["exp_avg"].clone(), st["exp_avg_sq"].clone()) for p, st in self.opt.state.items() if "exp_avg" in st}
-        # the true step count: replays advance only the device counter, so the host's is stale once any graph has run
-        steps = int(self.opt._step_dev.item()) if self.opt._step_dev is not None else self.opt._steps
-        st = TrainStep(self.kind, self.model, self.opt, None, self.gaw, self.ddp, graph=True, defer_wgrad=self.defer_wgrad, lens=lens)
-        st.static = st.batch = static
-        st.prepare()
+        # the capture's warm-up iterations train: weights and optimizer state are put back (into the same tensors) afterwards
+        snapshot = TrainingSnapshot([self.model], [self.opt]).take()
+        st = TrainStep(self.kind, self.model, self.opt, None, self.gaw, self.ddp, graph=True, defer_wgrad=self.defer_wgrad, lens=lens,
+                       static=static).prepare()
         torch.cuda.synchronize()
-        with torch.no_grad():
-            for p, w in zip(self.model.parameters(), saved_w):
-                p.copy_(w)
-            for p, s in self.opt.state.items():
-                if "exp_avg" in s:
-                    m, v = saved_opt.get(id(p), (None, None))
-                    if m is None:
-                        s["exp_avg"].zero_()
-                        s["exp_avg_sq"].zero_()
-                    else:
-                        s["exp_avg"].copy_(m)
-                        s["exp_avg_sq"].copy_(v)
-        self.opt._steps = steps
-        if self.opt._step_dev is not None:
-            self.opt._step_dev.fill_(steps)
-        self.opt.refresh_resident_weights()          # (the copies above bumped the weights' versions: the planes are re-split in place)
-        torch.cuda.synchronize()
-        del saved_w, saved_opt
+        snapshot.restore()
+        del snapshot
         self.capture_seconds += time.perf_counter() - t0
         self.captures += 1
         pool = tuple(st.stepper.pool)
         self.pool_bytes[bucket] = sum(4 * b.numel() if b.dtype != torch.int64 else 8 * b.numel() for b in static) + sum(
             seg["total_size"] for seg in torch.cuda.memory_snapshot() if tuple(seg.get("segment_pool_id", ())) == pool)
-        st.lens_host = torch.empty(len(bucket), dtype=torch.int32).pin_memory()     # staging for the live lengths (see __call__)
-        st.lens_copied = None
         self.steps[bucket] = st
         return st
 
@@ -880,13 +950,7 @@ class BucketedTrainStep:
             st = self._capture(bucket, batch)
         for d, b in zip(st.static, batch):
             _pad_into(d, b)
-        if st.lens_copied is not None:
-            st.lens_copied.synchronize()          # the previous asynchronous copy out of the pinned buffer has run (long since, as a rule)
-        for j, v in enumerate(need):
-            st.lens_host[j] = v
-        st.lens.copy_(st.lens_host, non_blocking=True)
-        st.lens_copied = torch.cuda.Event()
-        st.lens_copied.record()
+        st.set_live_lengths(need)
         st.stepper.run()
         self.replays += 1
         self.att = st.att
@@ -946,12 +1010,7 @@ class AdversarialGraphStep:
         else:
             g_phases = [("graph", self._g_forward), ("eager", lambda: ddp_syn.all_reduce_mean_(self.scalars)), ("graph", self._g_backward0)]
             if seg:
-                nseg = len(self.cuts.groups) + 1
-                for i in range(nseg):
-                    if i > 0:
-                        g_phases.append(("graph", lambda i=i: self._segs[i]()))
-                    last = i == nseg - 1
-                    g_phases.append(("eager", (lambda i=i: (ddp_syn.start_bucket(i), ddp_syn.finish())) if last else (lambda i=i: ddp_syn.start_bucket(i))))
+                g_phases += segmented_exchange_phases(self.cuts, ddp_syn, lambda i: self._segs[i]())
             else:
                 g_phases.append(("eager", self._g_exchange_packed))
             g_phases.append(("graph", self.opt_syn.step))
@@ -968,28 +1027,14 @@ class AdversarialGraphStep:
         self.g_stepper = PhasedStep(g_phases, graph=graph, drain=drain)
         self.d_stepper = PhasedStep(d_phases, graph=graph, drain=drain)
         if graph:
-            # warm up both kinds alternately (as the training loop runs them), then capture
-            s = torch.cuda.Stream()
-            s.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(s):
-                for _ in range(2):
-                    self.g_stepper._eager()
-                    self.d_stepper._eager()
-            torch.cuda.current_stream().wait_stream(s)
-            torch.cuda.synchronize()
-            self.g_stepper.warmup = self.d_stepper.warmup = 0
-            self.g_stepper.prepare()
-            self.d_stepper.prepare()
+            warm_up([self.g_stepper, self.d_stepper], 2)          # both kinds alternately, as the training loop runs them
+            self.g_stepper.capture()
+            self.d_stepper.capture()
             if self.defer is not None:
                 self.defer.finish_uploads()
 
     def _forward(self):
-        if self.kind == "text2mel":
-            mel, text, spk = self.static
-            pred, att = self.model(shift_right(mel), text, spk)
-            return pred, att, mel
-        mel, lin = self.static
-        return self.model(mel), None, lin
+        return KINDS[self.kind].forward(self.model, self.static)
 
     # ---- G
     def _g_forward(self):

@@ -85,6 +85,62 @@ def test_adversarial_train_captured_graphs(tmp_path):
     assert os.path.exists(ck)
 
 
+@pytest.mark.parametrize("resume", [False, True])
+def test_captured_adversarial_setup_starts_from_the_initial_or_checkpoint_state(tmp_path, resume):
+    """harness._adversarial_setup with CAPTURE_GRAPHS: the capture's warm-up iterations are undone.  Fresh run: both models as before the
+    set-up, all moments 0, step counts 0.  Resumed from the checkpoint of an eager run: models, every moment and both step counts (host and
+    device) are the checkpoint's, bitwise -- the optimizer state is loaded BEFORE the capture, so the graphs hold the loaded tensors.
+    Then one replayed iteration of each kind runs and advances its optimizer by one step."""
+    from spoofsv_amd import harness, train
+    step = "train_text2mel"
+    ck = None
+    if resume:
+        harness.adversarial_train(step, "conditional", _cfg(tmp_path, MAX_ITERATIONS=4, RATIO=2, VAL_EVERY_ITER=3), current_time="eager")
+        ck = torch.load(os.path.join(str(tmp_path), "checkpoints", "conditional", "adversarial", "eager", "text2mel_iteration_4.tar.pth"),
+                        map_location="cpu")
+    cfg = _cfg(tmp_path, RATIO=2, CAPTURE_GRAPHS=True)
+    dev = harness._device()
+    torch.manual_seed(4)
+    model, disc = harness._build(step, "conditional", cfg, True)
+    if resume:
+        model.load_state_dict(ck["model_state_dict"])
+        disc.load_state_dict(ck["disc_state_dict"])
+    else:
+        model.apply(train.init_weights)
+        disc.apply(train.init_weights)
+    model.to(dev).train()
+    disc.to(dev).train()
+    want = [{k: v.detach().cpu().clone() for k, v in m.state_dict().items()} for m in (model, disc)]
+    if resume:
+        for w, key in zip(want, ("model_state_dict", "disc_state_dict")):
+            assert all(torch.equal(w[k], ck[key][k]) for k in w)
+    src = harness.Prefetcher(harness.BatchSource(cfg, step, cfg["BATCH_SIZE"], None, pattern="conditional"), dev)
+    gaw = train.guided_attention_mat(cfg["MAX_TEXT_LEN"], cfg["MAX_FRAME_NUM"], device=dev)
+    stepper, opt_syn, opt_disc, pick = harness._adversarial_setup(step, cfg, dev, model, disc, src, gaw, ck, 0, 1)
+    assert stepper.g_stepper.plan is not None and stepper.d_stepper.plan is not None
+    for m, w in zip((model, disc), want):
+        for k, v in m.state_dict().items():
+            assert torch.equal(v.cpu(), w[k]), k
+    steps = []
+    for opt, key in ((opt_syn, "opt_state_dict_syn"), (opt_disc, "opt_state_dict_disc")):
+        saved = ck[key]["state"] if resume else {}
+        assert opt.state and (len(saved) > 0) == resume
+        for i, p in enumerate(opt.param_groups[0]["params"]):
+            for mk in ("exp_avg", "exp_avg_sq"):
+                if i in saved:
+                    assert torch.equal(opt.state[p][mk].cpu(), saved[i][mk]), (key, i, mk)
+                elif p in opt.state:
+                    assert not opt.state[p][mk].any(), (key, i, mk)
+        steps.append(max([int(sv["step"]) for sv in saved.values()], default=0))
+        assert opt._steps == steps[-1] and int(opt._step_dev.item()) == steps[-1]
+    if resume:
+        assert steps == [2, 2]                      # 4 iterations at RATIO 2: G D D G, checkpointed after the last
+    out = [float(v) for v in stepper.g_step()] + [float(v) for v in stepper.d_step()]
+    assert all(v == v and abs(v) != float("inf") for v in out), out
+    for opt, n in zip((opt_syn, opt_disc), steps):
+        assert float(opt.state_dict()["state"][0]["step"]) == n + 1
+
+
 def test_generator_accepts_critic_gradient_like_oracle():
     """dL/dY coming from the critic flows through the HIP generator exactly as through the oracle."""
     from spoofsv_amd import train

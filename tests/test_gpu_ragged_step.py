@@ -294,6 +294,46 @@ def test_a_second_bucket_keeps_adams_step_count():
         bt.close()
 
 
+@pytest.mark.parametrize("kind", ["ssrn", "text2mel"])
+def test_a_capture_leaves_model_and_optimizer_as_they_were_before_it(kind):
+    """After the first bucket's capture and before any replay the warm-up iterations are undone: every parameter equals a never-trained
+    twin bitwise, Adam's moments and device step count are 0, and the resident planes are current and byte for byte a fresh split of the
+    restored weights."""
+    from spoofsv_amd import resident
+    if kind == "ssrn":
+        ma, mb = _pair(lambda: SSRN(80, 65, 32))
+        batch, bucket, gaw = _ragged_ssrn(2, 30, 1, 65), (32,), None
+    else:
+        ma, mb = _pair(lambda: melSyn(34, True, 200, textemb_dim=16, freq_bins=80, hidden_dim=32))
+        batch, bucket, gaw = _ragged_t2m(2, 17, 30, 1), (24, 32), train.guided_attention_mat(186, 325, device=DEV)
+    oa = train.FusedAdam(ma.parameters(), 2e-4, (0.5, 0.9), 1e-6, capturable=True)
+    bt = train.BucketedTrainStep(kind, ma, oa, [bucket], gaw=gaw)
+    try:
+        st = bt._capture(bucket, batch)
+        assert st.stepper.plan is not None and (bt.captures, bt.replays, bt.eager) == (1, 0, 0)
+        for (k, pa), pb in zip(ma.named_parameters(), mb.parameters()):
+            assert torch.equal(pa, pb), k
+        assert oa.state                                             # (the warm-up created the moments)
+        for s in oa.state.values():
+            assert not s["exp_avg"].any() and not s["exp_avg_sq"].any()
+        assert int(oa._step_dev.item()) == 0 and oa._steps == 0
+        convs = [p for p in ma.parameters() if resident.eligible(p)]
+        plain = [p for p in convs if not getattr(p, "_ssv_transposed", False)]
+        assert plain and all(resident.lookup(p) is not None for p in plain)
+
+        # the planes are those of the RESTORED weights: a fresh split of every weight as it stands now writes the same bytes
+        planes = [t.clone() for t in oa._resident._planes]
+        resident.invalidate(convs)
+        assert all(resident.lookup(p) is None for p in plain)
+        oa.refresh_resident_weights()
+        torch.cuda.synchronize()
+        assert len(planes) == len(convs)
+        for p, was, now in zip(oa._resident.params, planes, oa._resident._planes):
+            assert torch.equal(was, now), tuple(p.shape)
+    finally:
+        bt.close()
+
+
 def test_other_batch_sizes_and_oversized_batches_run_eagerly():
     ma, mb = _pair(lambda: SSRN(80, 65, 32))
     oa = train.FusedAdam(ma.parameters(), 2e-4, (0.5, 0.9), 1e-6, capturable=True)

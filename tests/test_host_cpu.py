@@ -690,3 +690,108 @@ def test_bench_launch_check_under_the_torchrun_launcher():
     lines = [l for l in r.stdout.splitlines() if l.strip().startswith("{")]
     assert len(lines) == 1, r.stdout
     assert json.loads(lines[0])["ranks"] == list(range(8))
+
+
+# ------------------------------------------------------------------------------------------------ the capture lifecycle's host pieces
+class _WithBuffer(torch.nn.Module):
+    def __init__(self):
+        super().__init__()
+        self.lin = torch.nn.Linear(3, 2)
+        self.register_buffer("seen", torch.arange(4.0))
+
+
+def test_training_snapshot_restores_bitwise_into_the_same_tensors():
+    """train.TrainingSnapshot: weights, buffers, Adam moments and the step count come back bitwise, in the SAME tensors (captured
+    graphs hold their addresses); moments that only appeared after take() are zeroed; the device step counter is the true count."""
+    torch.manual_seed(0)
+    a, b = _WithBuffer(), torch.nn.Linear(2, 2)
+    oa = train.FusedAdam(a.parameters(), 2e-4, (0.5, 0.9), 1e-6, resident=False)
+    ob = train.FusedAdam(b.parameters(), 2e-4, (0.5, 0.9), 1e-6, resident=False)
+    for p in a.parameters():
+        oa.state[p] = {"step": torch.tensor(0.0), "exp_avg": torch.randn_like(p), "exp_avg_sq": torch.rand_like(p)}
+    oa._steps = 5
+
+    def tensors():
+        return ([t for m in (a, b) for t in list(m.parameters()) + list(m.buffers())]
+                + [oa.state[p][k] for p in a.parameters() for k in ("exp_avg", "exp_avg_sq")])
+    before = [(t, t.data_ptr(), t.detach().clone()) for t in tensors()]
+    assert len(before) == 2 + 1 + 2 + 4
+    snap = train.TrainingSnapshot([a, b], [oa, ob]).take()
+    with torch.no_grad():
+        for t, _, _ in before:
+            t.mul_(-3.0).add_(1.5)
+    for p in b.parameters():
+        ob.state[p] = {"step": torch.tensor(0.0), "exp_avg": torch.ones_like(p), "exp_avg_sq": torch.ones_like(p)}
+    oa._steps, ob._steps = 8, 3
+    assert not any(torch.equal(t, was) for t, _, was in before)
+    snap.restore()
+    for now, (t, ptr, was) in zip(tensors(), before):
+        assert now is t and t.data_ptr() == ptr and torch.equal(t, was)
+    for p in b.parameters():
+        assert not ob.state[p]["exp_avg"].any() and not ob.state[p]["exp_avg_sq"].any()
+    assert oa._steps == 5 and ob._steps == 0
+    # replays advance only the device counter: it is the one that counts, and both get it back
+    oa._step_dev = torch.tensor([9], dtype=torch.int32)
+    snap.take()
+    assert snap.steps == [9, 0]
+    oa._step_dev.fill_(12)
+    oa._steps = 11
+    snap.restore()
+    assert oa._steps == 9 and int(oa._step_dev) == 9
+
+
+class _PlanDDP:
+    """The part of an arena DataParallelRanks that a step's phase list is built from."""
+    arena, grad_scale = object(), 1.0
+
+    def __init__(self, cut_names):
+        self.cut_names, self.calls = cut_names, []
+
+    def start_bucket(self, i):
+        self.calls.append("start %d" % i)
+
+    def finish(self):
+        self.calls.append("finish")
+
+
+def test_data_parallel_phase_plan_is_graph_then_per_segment_graph_eager_then_graph():
+    want = {0: ["graph", "eager", "graph"],
+            1: ["graph", "eager", "graph", "eager", "graph"],
+            3: ["graph", "eager", "graph", "eager", "graph", "eager", "graph", "eager", "graph"]}
+    calls = {0: ["start 0", "finish"],
+             1: ["start 0", "seg 1", "start 1", "finish"],
+             3: ["start 0", "seg 1", "start 1", "seg 2", "start 2", "seg 3", "start 3", "finish"]}
+    for names in ([], ["a"], ["a", ["b", "c"], "d"]):
+        ddp = _PlanDDP(names)
+        st = train.TrainStep("ssrn", None, None, None, None, ddp, graph=False)
+        n = len(st.cuts.groups)
+        assert n == len(names)
+        assert [k for k, _ in st.stepper.phases] == want[n]
+        st._segs = [None] + [lambda i=i: ddp.calls.append("seg %d" % i) for i in range(1, n + 1)]
+        for k, fn in st.stepper.phases[1:-1]:          # (the first phase is forward + segment 0, the last is Adam)
+            before = len(ddp.calls)
+            fn()
+            if k == "eager":                              # only the last eager phase drains the collectives
+                assert ("finish" in ddp.calls[before:]) == (fn is st.stepper.phases[-2][1])
+        assert ddp.calls == calls[n]
+        # the same function serves the generator iteration of AdversarialGraphStep
+        assert [k for k, _ in train.segmented_exchange_phases(st.cuts, ddp, lambda i: None)] == want[n][1:-1]
+
+
+def test_step_kind_table_gives_the_keys_needs_shapes_and_forward_of_both_kinds():
+    import pytest
+    mel, text, spk, lin = torch.rand(2, 80, 30), torch.zeros(2, 1, 17, dtype=torch.long), torch.rand(2, 200, 1), torch.rand(2, 65, 120)
+    t2m, ssrn = train.KINDS["text2mel"], train.KINDS["ssrn"]
+    assert train.step_kind("train_text2mel") == "text2mel" and train.step_kind("train_ssrn") == "ssrn"
+    assert t2m.keys == ("data_0", "data_1", "data_2") and ssrn.keys == ("data_0", "data_1")
+    assert t2m.need((mel, text, spk)) == (17, 30) and ssrn.need((mel, lin)) == (30,)
+    assert t2m.static_shapes((24, 40), (mel, text, spk)) == [(2, 80, 40), (2, 1, 24), (2, 200, 1)]
+    assert ssrn.static_shapes((40,), (mel, lin)) == [(2, 80, 40), (2, 65, 160)]
+    assert (t2m.spec_live, t2m.att_live, ssrn.spec_live, ssrn.att_live) == ((1,), (0,), (0, 4), None)
+    with pytest.raises(ValueError, match=r"BucketedTrainStep: SSRN target has 119 frames for 30 mel frames \(want 4x\)"):
+        ssrn.need((mel, lin[:, :, :119]))
+    # the forward: teacher forcing for Text2Mel (the model sees the mel shifted right, the target is the mel itself), plain for SSRN
+    pred, att, target = t2m.forward(lambda m, t, s: (m, (t, s)), (mel, text, spk))
+    assert torch.equal(pred, train.shift_right(mel)) and att[0] is text and att[1] is spk and target is mel
+    pred, att, target = ssrn.forward(lambda m: m * 2, (mel, lin))
+    assert torch.equal(pred, mel * 2) and att is None and target is lin
