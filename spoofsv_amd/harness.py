@@ -25,7 +25,7 @@ import time
 import numpy as np
 import torch
 
-from . import ops, resident, train
+from . import ops, resident, synth, train
 from .critic import linDisc, melDisc
 from .tts import SSRN, melSyn
 
@@ -390,13 +390,12 @@ def _free_run(model, text_id, spk_emb, frames, freq_bins, graph=False, increment
     same values up to the arithmetic mode of the first few frames (short prefixes run the exact-fp32 kernels step by step)."""
     resident.ensure(model, ops._stream())       # frozen weights: split once, not once per conv call (~30 launches per step)
     if wide:              # many items per run: every layer of the column step one MFMA product over the batch (synth.WideSynthesizer);
-        from . import synth       # shared_texts = U: text_id holds U texts, item b of spk_emb speaks text b % U
+                          # shared_texts = U: text_id holds U texts, item b of spk_emb speaks text b % U
         return synth.free_run_wide(model, text_id, spk_emb, frames, shared_texts=shared_texts)
     if incremental:       # config key SYNTH_INCREMENTAL (default on in synthesize / generate_test_utterances): one new column
-        from . import synth       # per step instead of the whole prefix (spoofsv_amd/synth.py, IncrementalSynthesizer)
+                          # per step instead of the whole prefix (spoofsv_amd/synth.py, IncrementalSynthesizer)
         return synth.free_run_incremental(model, text_id, spk_emb, frames)
     if graph:
-        from . import synth
         return synth.free_run(model, text_id, spk_emb, frames)
     B = text_id.shape[0]
     dev = text_id.device

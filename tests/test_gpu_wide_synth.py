@@ -167,6 +167,11 @@ def test_wide_synthesis_matches_the_incremental_path(hidden, B, N, frames, condi
     with torch.no_grad():
         Y0, A0 = synth.free_run_incremental(m, text, spk, frames)
         Y1, A1 = synth.free_run_wide(m, text, spk, frames)
+    _agree_up_to_the_first_near_tie(Y0, A0, Y1, A1, frames, "wide vs incremental hidden=%d B=%d cond=%s" % (hidden, B, condition))
+
+
+def _agree_up_to_the_first_near_tie(Y0, A0, Y1, A1, frames, what):
+    """Frames before the first top-2 margin <= 1e-4 of (Y0, A0) must agree in arg-max; values within 2e-4 up to there."""
     assert Y1.shape == Y0.shape and A1.shape == A0.shape
     top = A0.topk(2, dim=1).values
     near_tie = ((top[:, 0] - top[:, 1]) <= 1e-4).any(0)
@@ -174,10 +179,47 @@ def test_wide_synthesis_matches_the_incremental_path(hidden, B, N, frames, condi
     assert cut >= 1
     assert torch.equal(A0.argmax(1)[:, :cut], A1.argmax(1)[:, :cut])
     ey, ea = rel_err(Y1[:, :, :cut + 1], Y0[:, :, :cut + 1]), rel_err(A1[:, :, :cut + 1], A0[:, :, :cut + 1])
-    print("wide vs incremental hidden=%d B=%d cond=%s: cut %d of %d, Y %.2e A %.2e" % (hidden, B, condition, cut, frames, ey, ea))
+    print("%s: cut %d of %d, Y %.2e A %.2e" % (what, cut, frames, ey, ea))
     assert ey < 2e-4 and ea < 2e-4
     if cut == frames:
         assert rel_err(Y1, Y0) < 2e-4 and rel_err(A1, A0) < 2e-4
+
+
+def test_a_mode_change_recaptures_on_the_cached_synthesizer(monkeypatch):
+    """fp32, split-fp16, fp32 again on ONE model object: the three free runs are served by the same cached WideSynthesizer, which
+    drops its graph at each mode change (the captured step holds the mode's kernels and plane addresses) and captures again with the
+    frame counter at ``frames``, where the run before left it -- the warm-up step of a capture runs at the current frame index, so
+    without a reset before it that step would write one frame past Yw and the histories.  The third result is the first bit for bit;
+    the second agrees with the first by the rule of test_wide_synthesis_matches_the_incremental_path."""
+    from spoofsv_amd import synth
+    B, N, frames = 9, 17, 33
+    m = _seeded_model(True, 32, 91)
+    text = torch.randint(2, 33, (B, 1, N), device=DEV)
+    text[:, :, -1] = 1
+    spk = 0.04 + 0.05 * torch.rand(B, 200, 1, device=DEV)
+    run, seen = synth.WideSynthesizer.run, []
+
+    def spy(self, *args, **kw):
+        before = (self.graph, int(self.t))
+        out = run(self, *args, **kw)
+        seen.append((self,) + before + (self.graph, int(self.t)))
+        return out
+
+    monkeypatch.setattr(synth.WideSynthesizer, "run", spy)
+    out = []
+    for precision in ("fp32", "f16x2", "fp32"):
+        with _mode(precision), torch.no_grad():
+            out.append(synth.free_run_wide(m, text, spk, frames))
+    assert len(seen) == 3 and seen[0][0] is seen[1][0] is seen[2][0]
+    assert seen[0][1] is None and seen[0][2] == 0                            # a fresh synthesizer
+    for k in (1, 2):
+        g_before, t_before, g_after, t_after = seen[k][1:]
+        assert g_before is seen[k - 1][3] and g_before is not None            # it came with the graph of the run before ...
+        assert t_before == frames == t_after                                  # ... and that run's frame counter,
+        assert g_after is not None and g_after is not g_before                # dropped the graph and captured a new one
+    (Y0, A0), (Y1, A1), (Y2, A2) = out
+    assert torch.equal(Y2, Y0) and torch.equal(A2, A0)
+    _agree_up_to_the_first_near_tie(Y0, A0, Y1, A1, frames, "wide f16x2 vs fp32 after a re-capture")
 
 
 @pytest.mark.parametrize("precision", MODES)

@@ -137,3 +137,161 @@ def test_byte_helper_equals_a_hand_count():
     assert total == want
     # the full-size run of 108 speakers x 20 sentences: 5.4 MB of history per item dominate
     assert 11e9 < synth.wide_synth_bytes(2160, 43, 326) < 13e9
+
+
+def _dump_synth_calls():
+    """tools/dump_synth_calls.py: the recorder of one synthesis step's library calls, shared with the tool that wrote the fixture."""
+    import importlib.util
+    import os
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("dump_synth_calls", os.path.join(root, "tools", "dump_synth_calls.py"))
+    tool = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(tool)
+    return tool, os.path.join(root, "tests", "golden", "synth_step_calls.json")
+
+
+def test_one_step_launches_what_the_committed_record_says():
+    """One step of IncrementalSynthesizer (50 calls) and of WideSynthesizer (26), conditioned and not, and the wide step with shared
+    texts in a split mode, recorded without a device: the same library entries in the same order with the same scalars, buffers,
+    parameters, weight copies and planes as tests/golden/synth_step_calls.json, which was recorded BEFORE the synthesizers shared a
+    column schedule.  The replayed step is what a free run's time goes to; the fixture is never regenerated from a later synth.py."""
+    import json
+    tool, path = _dump_synth_calls()
+    want = json.load(open(path))
+    got = json.loads(json.dumps(tool.collect()))
+    assert sorted(got) == sorted(want) == sorted(tool.CONFIGS) and len(want) == 5
+    for cfg in sorted(want):
+        assert len(want[cfg]) == (50 if cfg.startswith("incremental") else 26), cfg
+        for i, (g, w) in enumerate(zip(got[cfg], want[cfg])):
+            assert g == w, (cfg, i)
+        assert len(got[cfg]) == len(want[cfg]), cfg
+    split = want["wide/conditioned/shared_texts=3/f16x2"]                  # every launch is given the planes of its own weight
+    w_at = {"ssv_column_pwln_wide": 2, "ssv_column_highway_wide": 1}      # (w, w_packed) follow each other in both prototypes
+    pairs = [(c[w_at[c[0]]], c[w_at[c[0]] + 1]) for c in split if c[0] in w_at]
+    assert len(pairs) == 24 and all(w.endswith(".weight") and pl == "planes:" + w[len("param:"):] for w, pl in pairs)
+    assert tool.render(got) == open(path).read()
+
+
+def _small_melsyn(condition):
+    from spoofsv_amd.tts import melSyn
+    return melSyn(34, condition, 200 if condition else None, textemb_dim=16, freq_bins=80, hidden_dim=32).eval()
+
+
+@pytest.mark.parametrize("condition", [True, False])
+def test_column_schedule_is_the_models_forward_order(condition):
+    """column_schedule(model): 26 operations in the order of audioEncoder.forward / audioDecoder.forward (the modules' registration
+    order, read from named_modules()), each reading what the one before wrote, highway histories 0..15, speaker terms exactly when
+    the model is conditioned."""
+    from spoofsv_amd import synth
+    from spoofsv_amd.tts import highwayConv
+    m = _small_melsyn(condition)
+    sched = synth.column_schedule(m)
+    assert len(sched) == 26
+    names = {id(mod): name for name, mod in m.named_modules()}
+
+    def layers(part):                       # the convs (with the LayerNorm registered right after) and highway layers of a part, in order
+        mods = list(getattr(m, part).named_modules())
+        out = []
+        for (name, mod), nxt in zip(mods, mods[1:] + [(None, None)]):
+            if isinstance(mod, highwayConv):
+                out.append(("highway", (name,)))
+            elif type(mod).__name__ == "Conv1d" and not name.endswith(".conv") and name != "conv":
+                out.append(("link", (name, nxt[0])))
+        return [(kind, tuple(part + "." + n for n in ns)) for kind, ns in out]
+
+    want = layers("audio_encoder") + [("attention", ())] + layers("audio_decoder") + [("advance", ())]
+    assert [(op.kind, tuple(names[id(x)] for x in op.mods)) for op in sched] == want
+    assert [k for k, _ in want].count("link") == 8 and [k for k, _ in want].count("highway") == 16
+    # the buffers: a chain from mel_cur back to mel_cur, ping-pong between a and b except where the step leaves it
+    assert sched[0].src == "mel_cur" and sched[-1].dst == "mel_cur"
+    for prev, op in zip(sched, sched[1:]):
+        assert op.src == prev.dst
+    last_link = [op for op in sched if op.kind == "link"][-1]
+    for op in sched[:-1]:
+        if op.kind == "attention":
+            assert op.dst == "rq"
+        elif op is last_link:
+            assert op.dst == "y_cur" and op.act == 2
+        else:
+            assert op.dst in ("a", "b") and op.dst != op.src
+    assert sched[-2] is last_link
+    assert [op.hist for op in sched if op.kind == "highway"] == list(range(16))
+    assert all(op.hist is None for op in sched if op.kind != "highway")
+    assert [op.spk for op in sched if op.kind == "link"] == ([("s1" if condition else None), None, ("s2" if condition else None)] + [None] * 5)
+    assert [op.act for op in sched if op.kind == "link"] == [1, 1, 0, 0, 1, 1, 1, 2]
+    assert all(op.spk is None for op in sched if op.kind != "link")
+
+
+@pytest.mark.parametrize("attr,value", [("causal", False), ("dilation", 0), ("kernel_size", 1), ("dimension", 64)])
+@pytest.mark.parametrize("layer", ["audio_encoder.hci2.hc3", "audio_decoder.hc2"])
+def test_column_schedule_refuses_a_layer_the_step_cannot_run(layer, attr, value):
+    """One highway layer that is not causal, has no kernel of 3, another width or no positive dilation: refused, by the schedule and so
+    by both column synthesizers under their own names, before anything is allocated."""
+    from spoofsv_amd import synth
+    m = _small_melsyn(True)
+    setattr(m.get_submodule(layer), attr, value)
+    with pytest.raises(RuntimeError, match="unexpected highwayConv configuration"):
+        synth.column_schedule(m)
+    for cls in (synth.IncrementalSynthesizer, synth.WideSynthesizer):
+        with pytest.raises(RuntimeError, match=cls.__name__ + ": unexpected highwayConv configuration"):
+            cls(m, 6, 5, 4, "cpu")
+
+
+def test_synthesizers_share_one_lifecycle_and_one_fifo_cache_per_kind(monkeypatch):
+    """One ``run`` and one ``_capture`` for the three synthesizers; ``run`` resets the state BEFORE a capture as well as after it, on
+    every path (the warm-up step of a capture runs at the current frame index); the cache holds four synthesizers per kind, first in
+    first out, and rebuilds for another model object or moved parameters."""
+    import torch
+    from spoofsv_amd import synth
+    kinds = (synth.GraphSynthesizer, synth.IncrementalSynthesizer, synth.WideSynthesizer)
+    for cls in kinds:
+        assert cls.run is synth._Replayed.run and cls._capture is synth._Replayed._capture
+        assert "run" not in vars(cls) and "_capture" not in vars(cls)
+    m = _small_melsyn(False)
+    tool, _ = _dump_synth_calls()
+    with tool.stubbed(0):
+        g = synth.IncrementalSynthesizer(m, 6, 5, 4, "cpu")
+        log = []
+        monkeypatch.setattr(g, "_refresh", lambda: log.append("refresh"))
+        monkeypatch.setattr(g, "_load", lambda text, spk: log.append("load"))
+        monkeypatch.setattr(g, "_reset", lambda: log.append("reset"))
+        monkeypatch.setattr(g, "_result", lambda: log.append("result"))
+
+        class Graph:
+            def replay(self):
+                log.append("replay")
+
+        def capture():
+            assert log[-1] == "reset"
+            log.append("capture")
+            g.graph = Graph()
+        monkeypatch.setattr(g, "_capture", capture)
+        text = torch.zeros((6, 1, 5), dtype=torch.long)
+        g.run(text, None)
+        assert log == ["refresh", "load", "reset", "capture", "reset"] + ["replay"] * 4 + ["result"]
+        del log[:]
+        g.run(text, None)
+        assert log == ["refresh", "load", "reset"] + ["replay"] * 4 + ["result"]
+        g.graph = None                                   # an invalidation after a completed run: reset comes before the capture
+        del log[:]
+        g.run(text, None)
+        assert log[:5] == ["refresh", "load", "reset", "capture", "reset"]
+        with pytest.raises(RuntimeError, match=r"IncrementalSynthesizer was built for text ids of shape \(6, 1, 5\), got \(5, 1, 5\)"):
+            g.run(text[:5], None)
+    # the cache
+    built = []
+    monkeypatch.setattr(synth.IncrementalSynthesizer, "__init__", lambda self, model, *shape: built.append(shape) or
+                        self.__dict__.update(model=model, addresses=synth._addresses(model)))
+    monkeypatch.setitem(synth._CACHES, synth.IncrementalSynthesizer, {})
+    first = synth._cached(synth.IncrementalSynthesizer, m, 6, 5, 4, "cpu")
+    assert synth._cached(synth.IncrementalSynthesizer, m, 6, 5, 4, "cpu") is first and len(built) == 1
+    for frames in (5, 6, 7):
+        synth._cached(synth.IncrementalSynthesizer, m, 6, 5, frames, "cpu")
+    assert synth._cached(synth.IncrementalSynthesizer, m, 6, 5, 4, "cpu") is first and len(built) == 4
+    synth._cached(synth.IncrementalSynthesizer, m, 6, 5, 8, "cpu")              # a fifth: the oldest leaves
+    assert len(synth._CACHES[synth.IncrementalSynthesizer]) == 4
+    assert synth._cached(synth.IncrementalSynthesizer, m, 6, 5, 4, "cpu") is not first and len(built) == 6
+    again = synth._cached(synth.IncrementalSynthesizer, m, 6, 5, 8, "cpu")
+    m.audio_decoder.conv5.bias.data = m.audio_decoder.conv5.bias.data.clone()    # a parameter moved: a new synthesizer
+    assert synth._cached(synth.IncrementalSynthesizer, m, 6, 5, 8, "cpu") is not again
+    assert len(synth._CACHES[synth.IncrementalSynthesizer]) == 4 and synth._CACHE_MAX == 4

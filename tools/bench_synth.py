@@ -37,9 +37,9 @@ def wide_arms(speaker_counts, reps=5):
             B = S * U
             spk = (0.04 + 0.05 * torch.rand(S, 200, 1, device=dev)).repeat_interleave(U, dim=0).contiguous()
             big = timed(lambda: synth.free_run_incremental(m, text.repeat(S, 1, 1), spk, frames))
-            synth._ICACHE.clear()                            # its (B, T, C) histories: 5.3 MB per item
+            synth._CACHES[synth.IncrementalSynthesizer].clear()     # its (B, T, C) histories: 5.3 MB per item
             wide = timed(lambda: synth.free_run_wide(m, text, spk, frames, shared_texts=U))
-            synth._WCACHE.clear()
+            synth._CACHES[synth.WideSynthesizer].clear()
             torch.cuda.empty_cache()
             f = 1e3 / frames
             print("| %d | %d | %.3f | %.3f (%.3f-%.3f) | %.3f (%.3f-%.3f) | %.3g | %.2fx |" %
