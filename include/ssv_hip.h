@@ -435,6 +435,31 @@ int ssv_preemphasis(const float* x, float* y, float a, int B, int n, ssv_stream_
 int ssv_exp_affine(const float* x, float* y, float a, float b, long n, ssv_stream_t stream);
 int ssv_log_norm(const float* x, float* y, float ref_db, float max_db, long n, ssv_stream_t stream);
 
+/* ---- FFT back end of the vocoder (additions; ABI version unchanged) -------------------------------------------------------------
+ * The same transforms as the basis convolutions above -- librosa.stft / istft with a periodic Hann window, centred frames -- as
+ * real FFTs that keep a tile of frames in LDS: fp32 throughout, no atomics, independent of ssv_set_precision.  n_fft: a power of two
+ * in [64, 2048], else -2; 0 < hop <= n_fft.  Spectra as above, (B, 2F, T).  Inverse frames are FRAME-major here, (B, T, N): a private
+ * workspace between ssv_istft_frames_fft and its two consumers.  tab: the ssv_fft_tables_floats(n_fft) floats that
+ * ssv_fft_tables_host writes (host only, the caller uploads them): the window, then cos and sin of 2 pi k / n_fft for k < n_fft / 2,
+ * computed in double and rounded once.  ssv_fft_frame_tile (host only): consecutive frames one workgroup owns, or -2.
+ * Codes: NULL pointers, non-positive sizes, hop > n_fft, hop * (T - 1) <= n_fft / 2, n <= n_fft / 2: -1. */
+size_t ssv_fft_tables_floats(int n_fft);
+int ssv_fft_tables_host(float* out, int n_fft);
+int ssv_fft_frame_tile(int n_fft);
+/* y (B, n) -> spec (B, 2F, T), T = 1 + n / hop: reflect padding by n_fft / 2, window and real FFT in one launch (ssv_frame_signal and
+ * the forward basis conv). */
+int ssv_stft_fft(const float* y, const float* tab, float* spec, int B, int n, int n_fft, int hop, int T, ssv_stream_t stream);
+/* spec (B, 2F, T) -> windowed inverse frames fr (B, T, N); the imaginary parts of the DC and Nyquist rows are ignored (numpy.fft.irfft).
+ * fr must be 8-byte aligned (stored two floats at a time), else -1. */
+int ssv_istft_frames_fft(const float* spec, const float* tab, float* fr, int B, int n_fft, int T, ssv_stream_t stream);
+/* ssv_ola_signal for frame-major frames: fr (B, T, N) -> y (B, hop * (T - 1)), frames added in increasing index. */
+int ssv_ola_signal_fm(const float* fr, const float* inv_env, float* y, int B, int N, int T, int hop, ssv_stream_t stream);
+/* One Griffin-Lim round trip in one launch: what ssv_ola_frames does to fr (B, T, N), then window, real FFT and the phase step of
+ * ssv_gl_project.  Writes reb (B, 2F, T), the rebuilt spectrum (the next call's tprev; must not alias it), and
+ * proj = mag * a / (|a| + 1e-16), a = reb - alpha * tprev (tprev NULL = 0). */
+int ssv_gl_step_fft(const float* fr, const float* inv_env, const float* tab, const float* mag, const float* tprev, float alpha,
+                    float* reb, float* proj, int B, int n_fft, int T, int hop, ssv_stream_t stream);
+
 /* ---- Speaker-verification front end: waveform -> GE2E features (additions; ABI version unchanged) ---------------------------
  * Replaces GE2E/data_preprocess.py:45-60 (`librosa.core.load(path, sr)`, `librosa.effects.trim(utter, 30)`, `librosa.core.stft`,
  * `np.abs(S)**2`, `np.dot(mel_basis, S)`, `np.log10(. + 1e-6)`, `S[:, :tisv_frame]` / `S[:, -tisv_frame:]`) for ragged batches:

@@ -741,7 +741,7 @@ def synthesize(pattern, cfg, spec_dir, current_time=None, texts=None, spk_emb=No
     if cfg.get("VOCODE", True):
         from scipy.io import wavfile               # what librosa 0.7.0's output.write_wav calls (synthesize.py:147)
         from .vocoder import Vocoder
-        voc = Vocoder(cfg["STFT"]["FFT_LENGTH"], cfg["STFT"]["HOP_LENGTH"], dev)
+        voc = Vocoder(cfg["STFT"]["FFT_LENGTH"], cfg["STFT"]["HOP_LENGTH"], dev, transform=cfg.get("VOCODER_TRANSFORM", "dft"))
     syn_list = os.path.join(cfg.get("DATA_ROOT_DIR", ""), "data_path", "ordinary", "wav.path.synthesize")
     if texts is None and os.path.exists(syn_list):
         # synthesize.py:62,90-147 proper: the 'synthesize' split of the corpus in batches of 8 -- free run for as many frames as
@@ -845,7 +845,7 @@ def generate_test_utterances(cfg, current_time, eval_utt_num=20, speakers=None, 
     if speakers is None:
         d = cfg["SPK_EMB_DIR"]
         speakers = {f[:-4]: np.load(os.path.join(d, f)) for f in sorted(os.listdir(d)) if f.endswith(".npy")}
-    voc = Vocoder(cfg["STFT"]["FFT_LENGTH"], cfg["STFT"]["HOP_LENGTH"], dev)
+    voc = Vocoder(cfg["STFT"]["FFT_LENGTH"], cfg["STFT"]["HOP_LENGTH"], dev, transform=cfg.get("VOCODER_TRANSFORM", "dft"))
     save_dir = os.path.join(cfg["SRC_ROOT_DIR"], "test", str(current_time), "spoof_data")
     frames = (max_frames or cfg["MAX_FRAME_NUM"]) + 1                   # first frame + MAX_FRAME_NUM further steps (:110-116)
     sr, out = cfg["SAMPLING_RATE"], {}

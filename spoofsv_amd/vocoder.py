@@ -17,8 +17,24 @@ frame axis on the matrix cores.
 
 The basis entries carry 16 mantissa bits (bf16 hi + lo), so one transform is accurate to ~1e-5 of the signal norm
 (librosa's complex64 FFT: ~1e-7); Griffin-Lim's own spectral inconsistency is 1e-1..1e-2, four orders above that.
+
+``Vocoder(..., transform="fft")`` (opt-in; n_fft a power of two from 64 to 2048) is the counterpart of that last sentence: an FFT
+needs no matrix cores to be batched across the frame axis.  A workgroup of ``csrc/fft.hip`` keeps a tile of consecutive frames
+(16 at n_fft = 1024) in LDS, runs their radix-2 stages there in fp32 -- ~25 kFLOP per frame instead of 2.1 MFLOP -- and touches
+memory once on the way in and once on the way out, in runs along the frame axis.  A Griffin-Lim iteration is two launches:
+``ssv_istft_frames_fft`` (spectrum -> windowed inverse frames, frame-major) and ``ssv_gl_step_fft`` (overlap-add, envelope, trim,
+reflect-pad, re-frame, window, FFT and the phase projection), 2*n_iter + 3 per call.  It has no arithmetic mode (bitwise the
+same under every ``ssv_set_precision``) and leaves ~2e-7 of the peak against float64 where the basis product leaves ~1e-5.
+Measured in one process on the same inputs (``tools/bench_vocoder.py --transform both``, ``profiles/fft_vocoder.txt``; 64 iterations,
+T = 1300): 1.74 ms per utterance at B = 16 against 2.17 ms for the basis product (0.80x), 1.66 against 2.37 at B = 20, 4.42 against
+4.59 at B = 1, eager (replayed: within 4 % of that) -- faster, but nowhere near the few tenths of a millisecond its memory traffic alone would
+take.  Why has not been measured (no counters, no kernel trace); the likely cause is latency: 1,312 workgroups of 512 threads, one
+or two per CU, a barrier per stage.  The default stays "dft".
+
 There is no CPU fallback: tensors must be on a ROCm device.
 """
+
+import operator
 
 import numpy as np
 import torch
@@ -27,6 +43,7 @@ from . import _lib, ops, resident
 from .ops import _p
 
 _F32 = torch.float32
+FFT_MIN, FFT_MAX = 64, 2048      # n_fft of transform="fft": a power of two in this range (csrc/fft_core.h)
 
 
 def _bases(n_fft):
@@ -96,18 +113,30 @@ def trim_silence(y, top_db=60.0, frame_length=2048, hop_length=512):
 class Vocoder:
     """STFT / ISTFT / Griffin-Lim on one ROCm device for a fixed (n_fft, hop)."""
 
-    def __init__(self, n_fft=1024, hop=256, device="cuda"):
+    def __init__(self, n_fft=1024, hop=256, device="cuda", transform="dft"):
+        if transform not in ("dft", "fft"):
+            raise ValueError("spoofsv_amd.vocoder: transform must be 'dft' or 'fft', got %r" % (transform,))
+        if transform == "fft":
+            n_fft, hop = operator.index(n_fft), operator.index(hop)       # any integer type (numpy.int64 ...); a float is a TypeError
+        if transform == "fft" and not (FFT_MIN <= n_fft <= FFT_MAX and n_fft & (n_fft - 1) == 0):
+            raise ValueError("spoofsv_amd.vocoder: transform='fft' needs n_fft a power of two from %d to %d, got %r" % (FFT_MIN, FFT_MAX, n_fft))
         dev = torch.device(device)
         if dev.type != "cuda":
             raise RuntimeError("spoofsv_amd.vocoder: needs a ROCm device (no CPU fallback exists), got %s" % dev)
         if n_fft % 2 or hop <= 0 or hop > n_fft:
             raise ValueError("n_fft must be even and 0 < hop <= n_fft")
-        self.n_fft, self.hop, self.F, self.device = n_fft, hop, n_fft // 2 + 1, dev
-        fwd, inv = _bases(n_fft)
-        self.w_fwd = torch.from_numpy(fwd).to(dev)
-        self.w_inv = torch.from_numpy(inv).to(dev)
-        self._planes = resident.ResidentWeights([self.w_fwd, self.w_inv])   # constants: split once
-        self._planes.refresh(ops._stream())
+        self.n_fft, self.hop, self.F, self.device, self.transform = n_fft, hop, n_fft // 2 + 1, dev, transform
+        if transform == "fft":                                              # no bases, no resident planes: one table of 2 N floats
+            tab = np.empty(_lib.query("ssv_fft_tables_floats", n_fft), dtype=np.float32)
+            _lib.call("ssv_fft_tables_host", tab.ctypes.data, n_fft)
+            self._tab = torch.from_numpy(tab).to(dev)
+            self.frame_tile = int(_lib.lib().ssv_fft_frame_tile(n_fft))
+        else:
+            fwd, inv = _bases(n_fft)
+            self.w_fwd = torch.from_numpy(fwd).to(dev)
+            self.w_inv = torch.from_numpy(inv).to(dev)
+            self._planes = resident.ResidentWeights([self.w_fwd, self.w_inv])   # constants: split once
+            self._planes.refresh(ops._stream())
         self._env = {}
         self._mel = {}
         self._graphs = {}
@@ -144,7 +173,22 @@ class Vocoder:
 
     def stft(self, y):
         """librosa.stft(y, n_fft, hop_length): (B, n) -> (B, 2F, T), real rows then imaginary rows."""
+        if self.transform == "fft":
+            if not (y.is_cuda and y.dtype == _F32 and y.dim() == 2 and y.is_contiguous()):
+                raise RuntimeError("spoofsv_amd.vocoder: waveform must be a contiguous float32 ROCm tensor (B, n)")
+            B, n = y.shape
+            T = 1 + n // self.hop
+            spec = torch.empty((B, 2 * self.F, T), dtype=_F32, device=y.device)
+            _lib.call("ssv_stft_fft", _p(y), _p(self._tab), _p(spec), B, n, self.n_fft, self.hop, T, ops._stream())
+            return spec
         return self._dft(self.w_fwd, self.frames(y))
+
+    def _inv_frames_fft(self, spec, out=None):
+        """(B, 2F, T) -> windowed inverse frames, FRAME-major (B, T, N): the private workspace of the FFT back end."""
+        B, _, T = spec.shape
+        fr = out if out is not None else torch.empty((B, T, self.n_fft), dtype=_F32, device=spec.device)
+        _lib.call("ssv_istft_frames_fft", _p(spec), _p(self._tab), _p(fr), B, self.n_fft, T, ops._stream())
+        return fr
 
     def magnitude(self, spec):
         self._check_spec(spec, 2 * self.F)
@@ -157,6 +201,10 @@ class Vocoder:
         """librosa.istft(S, hop_length): (B, 2F, T) -> (B, hop*(T-1))."""
         self._check_spec(spec, 2 * self.F)
         B, _, T = spec.shape
+        if self.transform == "fft":
+            y = torch.empty((B, self.hop * (T - 1)), dtype=_F32, device=spec.device)
+            _lib.call("ssv_ola_signal_fm", _p(self._inv_frames_fft(spec)), _p(self._inv_env(T)), _p(y), B, self.n_fft, T, self.hop, ops._stream())
+            return y
         fr = self._dft(self.w_inv, spec)
         y = torch.empty((B, self.hop * (T - 1)), dtype=_F32, device=spec.device)
         _lib.call("ssv_ola_signal", _p(fr), _p(self._inv_env(T)), _p(y), B, self.n_fft, T, self.hop, ops._stream())
@@ -182,6 +230,21 @@ class Vocoder:
         alpha = momentum / (1.0 + momentum)
         proj = torch.empty((B, 2 * F, T), dtype=_F32, device=S.device)
         reb = [torch.empty_like(proj), torch.empty_like(proj)]
+        if self.transform == "fft":      # 2 * n_iter + 3 launches: the inverse FFT, then everything up to the next projection in one
+            fr = torch.empty((B, T, N), dtype=_F32, device=S.device)
+            _lib.call("ssv_gl_project", _p(S), _p(angles0), None, 0.0, _p(proj), B, F, T, st)
+            for it in range(n_iter):
+                cur = reb[it & 1]
+                self._inv_frames_fft(proj, fr)
+                _lib.call("ssv_gl_step_fft", _p(fr), _p(env), _p(self._tab), _p(S), _p(reb[1 - (it & 1)]) if it else None, alpha,
+                          _p(cur), _p(proj), B, N, T, hop, st)
+                if trace is not None:
+                    m = self.magnitude(cur)
+                    trace.append(float((m - S).norm() / S.norm()))
+            self._inv_frames_fft(proj, fr)
+            y = torch.empty((B, hop * (T - 1)), dtype=_F32, device=S.device)
+            _lib.call("ssv_ola_signal_fm", _p(fr), _p(env), _p(y), B, N, T, hop, st)
+            return y
         fa = torch.empty((B, N, T), dtype=_F32, device=S.device)
         fb = torch.empty_like(fa)
         _lib.call("ssv_gl_project", _p(S), _p(angles0), None, 0.0, _p(proj), B, F, T, st)
@@ -201,7 +264,7 @@ class Vocoder:
 
     def griffinlim_graph(self, S, angles0=None, n_iter=64, momentum=0.99):
         """``griffinlim`` replayed from a captured hipGraph (one per (B, T, n_iter, momentum)): the 4*n_iter + 3 launches
-        of a small batch are launch-bound when issued one by one (B = 1, T = 1300: 9.3 ms eager)."""
+        (transform="fft": 2*n_iter + 3) of a small batch are launch-bound when issued one by one (B = 1, T = 1300: 9.3 ms eager)."""
         self._check_spec(S, self.F)
         B, F, T = S.shape
         key = (B, T, int(n_iter), float(momentum))

@@ -90,7 +90,8 @@ def collect(precisions=(0, 1, 2)):
     L = _lib.lib()
     protos = _lib.parse_header()
     raw = ctypes.CDLL(_lib.LIBPATH)
-    queries = sorted(n for n, (ret, _, _) in protos.items() if ret is ctypes.c_size_t)
+    # buffer sizes in bytes only: a size_t that counts something else (ssv_fft_tables_floats) is no workspace query
+    queries = sorted(n for n, (ret, _, _) in protos.items() if ret is ctypes.c_size_t and n.endswith(("_workspace", "_bytes")))
     assert len(queries) == 31, queries
     queries += ["ssv_conv1d_bwd_weight_multi_ok", "ssv_conv1d_bwd_weight_multi_splits", "ssv_ln_bwd_partial_rows"]
     saved_env = {v: os.environ.pop(v) for v in TUNING_VARS if v in os.environ}
