@@ -15,35 +15,40 @@ import weakref
 
 import torch
 
-_SLOTS = {}      # parameter data_ptr -> (arena weakref, offset, numel, parameter weakref)
+from .resident import param_of
+
+
+class _Slot:
+    """``p._ssv_grad_slot``: the slot of parameter ``p`` in the most recently built arena over it -- that arena (weakly), offset, size."""
+    __slots__ = ("arena", "off", "numel")
+
+    def __reduce__(self):                # a pickled or deep-copied parameter carries no slot
+        return type(None), ()
 
 
 def _entry(t):
-    e = _SLOTS.get(t.data_ptr())
-    if e is None or e[2] != t.numel():          # same storage start and size (nn.Linear weights arrive with a trailing unit axis)
+    p = param_of(t)
+    e = getattr(p, "_ssv_grad_slot", None)
+    arena = e.arena() if e is not None else None
+    # a live arena where the parameter is, and the parameter itself or a dense view of all of it (nn.Linear weights arrive with a trailing unit axis)
+    if arena is None or arena.flat.device != p.device or not t.is_contiguous() or t.data_ptr() != p.data_ptr() or t.numel() != e.numel:
         return None
-    arena, param = e[0](), e[3]()
-    if arena is None or param is None or param.data_ptr() != t.data_ptr():
-        # the arena or the parameter it was built for is gone (its memory may belong to another tensor by now), or the
-        # parameter was moved: the slot is stale
-        _SLOTS.pop(t.data_ptr(), None)
-        return None
-    g = param.grad
-    if g is not None and g.data_ptr() == arena.flat.data_ptr() + 4 * e[1]:
+    g = p.grad
+    if g is not None and g.data_ptr() == arena.flat.data_ptr() + 4 * e.off:
         # The slot already HOLDS a gradient of this parameter (a backward without zero_grad(set_to_none=True) before it).  A
         # kernel writing there again would clobber what p.grad aliases and autograd would then add the slot to itself.  Hand
         # out no slot: the operator allocates a fresh tensor and autograd accumulates it into p.grad -- i.e. into the arena.
         return None
-    if e[1] in arena.claimed:
+    if e.off in arena.claimed:
         # The slot was handed to another user of this parameter EARLIER IN THE SAME BACKWARD: autograd's AccumulateGrad runs only
         # after all users of a leaf have delivered, so p.grad is still None and the test above cannot see it.  The mark is set
         # by view() / block() and cleared by the parameter's post-accumulate hook.  Same answer: no slot, autograd sums.
         return None
-    return arena, e[1], e[2]
+    return arena, e.off, e.numel
 
 
 def view(w, claim=True):
-    """The arena slot of parameter ``w`` (looked up by address and shape) as a tensor of ``w``'s shape, or None.  ``claim``: the
+    """The arena slot of parameter ``w`` (or of the parameter ``w`` is a dense view of) as a tensor of ``w``'s shape, or None.  ``claim``: the
     caller is a backward operator about to write the gradient there (the slot is not handed out again before autograd has
     accumulated it); False only looks."""
     e = _entry(w)
@@ -53,13 +58,6 @@ def view(w, claim=True):
     if claim:
         arena.claimed.add(off)
     return arena.flat[off:off + n].view(w.shape)
-
-
-def claimed(w):
-    """True when ``w`` has an arena slot that a backward operator already took in the backward in progress."""
-    e = _SLOTS.get(w.data_ptr())
-    arena = e[0]() if e is not None else None
-    return arena is not None and e[1] in arena.claimed
 
 
 def block(params, rows, cols, claim=True):
@@ -138,7 +136,8 @@ class GradArena:
 
         for p in self.params:
             o, n = self.slots[id(p)]
-            _SLOTS[p.data_ptr()] = (ref, o, n, weakref.ref(p))
+            e = p._ssv_grad_slot = _Slot()
+            e.arena, e.off, e.numel = ref, o, n
             if p.requires_grad:
                 # AccumulateGrad has run for p (all of its users in this backward have delivered): its slot may be handed out again
                 self._hooks.append(p.register_post_accumulate_grad_hook(unclaim(o)))
@@ -150,9 +149,9 @@ class GradArena:
         """Detach the arena from its parameters: hooks removed, slots forgotten.  Idempotent."""
         _remove_hooks(self._hooks)
         for p in self.params:
-            e = _SLOTS.get(p.data_ptr())
-            if e is not None and e[0]() is self:
-                _SLOTS.pop(p.data_ptr())
+            e = getattr(p, "_ssv_grad_slot", None)
+            if e is not None and e.arena() is self:         # (a later arena over the same model keeps its own)
+                del p._ssv_grad_slot
 
     def bucket(self, i):
         a, b = self.ranges[i]

@@ -8,6 +8,7 @@ Layout convention: activations are (B, C, T) float32 with contiguous rows (strid
 stride(1) == T); the batch stride is free, so channel slices of a wider tensor are passed without
 copies.  Each Function cites the reference code its forward replaces.
 """
+import collections
 import contextlib
 import ctypes
 
@@ -147,6 +148,28 @@ def _needs_grad(ctx):
 
 
 # ------------------------------------------------------------------------------------------- deferred weight gradients
+class _WgradSlot:
+    """The job tables of the i-th weight-gradient launch of a step (``DeferredWgrad.slots``)."""
+    __slots__ = ("pinned", "eager", "copied", "upload_pending", "captured", "captured_in_use")
+
+    def __init__(self, cap, dev):
+        self.pinned = torch.empty(cap, dtype=torch.uint8).pin_memory()         # the table as ``flush`` fills it, copied from at every launch
+        self.eager = torch.empty(cap, dtype=torch.uint8, device=dev)           # device table of the eager launches
+        self.copied = None                                                     # event after the last copy out of the pinned table
+        self.upload_pending = False                                            # a capture's upload out of the pinned table is pending (finish_uploads)
+        # Device table of the CAPTURED launch, written once.  A table of its own: an eager iteration through the same DeferredWgrad after
+        # the capture -- a logged or debug step -- rewinds the cursor and rewrites the slots' eager tables, and the replays must keep
+        # reading the captured addresses.  (Allocated by the eager warm-up, outside any capture: a block from the capture's own pool may
+        # be the recycled memory of an earlier activation OF THE SAME CAPTURE, whose producer would overwrite the table at every replay
+        # -- the upload in flush is not part of the captured order.)
+        self.captured = torch.empty(cap, dtype=torch.uint8, device=dev)
+        self.captured_in_use = False                                           # that table is in use: a captured step reads it (release_capture)
+
+
+# one queued weight gradient: what the launch reads, the ADDRESSES it writes + their storages (see add), the tap shifts, the operand scale lists
+_WgradJob = collections.namedtuple("_WgradJob", "dy x part dw_ptr pg_ptr storages shift dy_amax x_amax")
+
+
 class DeferredWgrad:
     """Weight gradients of equal-shaped layers, collected during backward and computed by ONE launch per shape at ``flush``
     (include/ssv_hip.h, "Weight gradients of several equal-shaped conv layers in ONE launch"): nothing downstream in backward
@@ -162,10 +185,9 @@ class DeferredWgrad:
 
     def __init__(self):
         self.jobs = {}
-        self.slots = []                # [pinned uint8 table, device table (eager launches), event after the last copy out of the pinned table,
-                                       #  a capture's upload pending, device table of the CAPTURED launch (written once), that table in use]
+        self.slots = []                # _WgradSlot per launch of a step
         self.cursor = 0
-        self.pending = set()           # addresses of the parameters whose gradient is queued and not yet flushed
+        self.pending = set()           # the parameters whose gradient is queued and not yet flushed
         self._side = None              # stream for the table uploads of a capture (see flush)
 
     def __enter__(self):
@@ -186,7 +208,7 @@ class DeferredWgrad:
         if self._side is not None:
             self._side.synchronize()
         for slot in self.slots:
-            slot[3] = False
+            slot.upload_pending = False
 
     def release_capture(self):
         """The captured step that read this instance's frozen job tables has been dropped (its hipGraphs destroyed): the tables may be
@@ -194,8 +216,8 @@ class DeferredWgrad:
         if self._side is not None:
             self._side.synchronize()
         for slot in self.slots:
-            slot[3] = False
-            slot[5] = False
+            slot.upload_pending = False
+            slot.captured_in_use = False
         self.jobs = {}                 # (a capture that failed half way may have left its queue behind)
         self.pending.clear()
 
@@ -211,12 +233,12 @@ class DeferredWgrad:
             # A parameter used twice in one backward: p.grad is still None at its second use (AccumulateGrad runs after all users),
             # and autograd would ADD the first, not yet computed, deferred gradient to the second.  Nothing in the models here
             # shares a parameter; refuse loudly instead of computing a wrong sum.
-            ptrs = [p.data_ptr() for p in params if p is not None]
-            if any(q in _DEFER.pending for q in ptrs):
+            owners = [resident.param_of(p) for p in params if p is not None]
+            if any(q in _DEFER.pending for q in owners):
                 raise RuntimeError("DeferredWgrad: a parameter is used by two operators of one backward pass; deferred (batched) "
                                    "weight gradients cannot be summed by autograd -- build the step with defer_wgrad=False")
             if ok:
-                _DEFER.pending.update(ptrs)
+                _DEFER.pending.update(owners)
         return ok
 
     def add(self, dy, dy_bs, x, x_bs, dw, part, pg, k, dilation, causal, n2, nblk, dy_amax=None, x_amax=None):
@@ -227,8 +249,8 @@ class DeferredWgrad:
         # dw and pg are what the caller hands to autograd, which adopts a returned gradient as ``p.grad`` only while nobody else
         # holds the tensor OBJECT or a view of it (otherwise it clones -- here: the not yet computed values).  The queue keeps
         # the address and the STORAGE alive, not the tensors.
-        self.jobs.setdefault(key, []).append((dy, x, part, dw.data_ptr(), pg.data_ptr(), (dw.untyped_storage(), pg.untyped_storage()), tuple(sh),
-                                              dy_amax, x_amax))
+        self.jobs.setdefault(key, []).append(_WgradJob(dy, x, part, dw.data_ptr(), pg.data_ptr(), (dw.untyped_storage(), pg.untyped_storage()),
+                                                       tuple(sh), dy_amax, x_amax))
 
     def _slot(self, nbytes, dev):
         capturing = torch.cuda.is_current_stream_capturing()
@@ -237,20 +259,19 @@ class DeferredWgrad:
                 raise RuntimeError("DeferredWgrad: run one eager iteration before capturing (job tables are pinned buffers, "
                                    "which cannot be allocated during a hipGraph capture)")
             cap = max(4096, nbytes)
-            self.slots.append([torch.empty(cap, dtype=torch.uint8).pin_memory(), torch.empty(cap, dtype=torch.uint8, device=dev), None, False,
-                               torch.empty(cap, dtype=torch.uint8, device=dev), False])
+            self.slots.append(_WgradSlot(cap, dev))
         slot = self.slots[self.cursor]
-        if slot[0].numel() < nbytes or slot[1].device != dev:
+        if slot.pinned.numel() < nbytes or slot.eager.device != dev:
             raise RuntimeError("DeferredWgrad: the sequence of weight-gradient launches changed between iterations")
         if capturing:
             # (HIP refuses an event synchronize from a capturing thread: "operation not permitted on an event last recorded in a
             # capturing stream", also for events of other streams.)  The pinned table is free unless an EARLIER capture's upload from
             # it is still in flight on the side stream: captures must be separated by finish_uploads().
-            if slot[3]:
+            if slot.upload_pending:
                 raise RuntimeError("DeferredWgrad: call finish_uploads() after a capture before capturing again")
-            slot[3] = True
-        elif slot[2] is not None:
-            slot[2].synchronize()          # the previous copy out of this pinned table has executed (launch stream, or a capture's side stream)
+            slot.upload_pending = True
+        elif slot.copied is not None:
+            slot.copied.synchronize()          # the previous copy out of this pinned table has executed (launch stream, or a capture's side stream)
         self.cursor += 1
         return slot
 
@@ -261,44 +282,40 @@ class DeferredWgrad:
             n = len(jobs)
             table = (_lib.WgradJob * n)()
             f16 = _f16()
-            for t, (dy, x, part, dw_ptr, pg_ptr, _, sh, dy_amax, x_amax) in zip(table, jobs):
-                t.dy, t.x, t.dw, t.part, t.pgrads = dy.data_ptr(), x.data_ptr(), dw_ptr, part.data_ptr(), pg_ptr
-                t.shift[0], t.shift[1], t.shift[2] = sh
+            for t, j in zip(table, jobs):
+                t.dy, t.x, t.dw, t.part, t.pgrads = j.dy.data_ptr(), j.x.data_ptr(), j.dw_ptr, j.part.data_ptr(), j.pg_ptr
+                t.shift[0], t.shift[1], t.shift[2] = j.shift
                 if f16:
-                    if dy_amax is None or x_amax is None:
+                    if j.dy_amax is None or j.x_amax is None:
                         raise RuntimeError("DeferredWgrad: a job was queued without operand scales in the split-fp16 mode")
-                    t.dy_amax, t.x_amax, t.dy_namax, t.x_namax = dy_amax.data_ptr(), x_amax.data_ptr(), dy_amax.numel(), x_amax.numel()
+                    t.dy_amax, t.x_amax, t.dy_namax, t.x_namax = j.dy_amax.data_ptr(), j.x_amax.data_ptr(), j.dy_amax.numel(), j.x_amax.numel()
             raw = bytes(table)
             slot = self._slot(len(raw), dev)
-            slot[0][:len(raw)].copy_(torch.frombuffer(bytearray(raw), dtype=torch.uint8))
+            slot.pinned[:len(raw)].copy_(torch.frombuffer(bytearray(raw), dtype=torch.uint8))
             if torch.cuda.is_current_stream_capturing():
                 # The table of a captured launch is CONSTANT (the addresses of the capture's own tensors): it is uploaded once, now,
                 # on a stream outside the capture, instead of by a copy node that every replay would run in front of the launch
-                # (11 such nodes of ~4 us per training step).  ``finish_uploads`` (after the capture) waits for it.
-                # It goes into the slot's SECOND device table, which eager iterations never write: an eager iteration through the same
-                # DeferredWgrad after the capture -- a logged or debug step -- rewinds the cursor and rewrites the slots' first tables,
-                # and the replays must keep reading the captured addresses.  (Allocated by the eager warm-up, outside any capture: a
-                # block from the capture's own pool may be the recycled memory of an earlier activation OF THE SAME CAPTURE, whose
-                # producer would overwrite the table at every replay -- the upload below is not part of the captured order.)
-                if slot[5]:
+                # (11 such nodes of ~4 us per training step).  ``finish_uploads`` (after the capture) waits for it.  It goes into the
+                # slot's ``captured`` table, which eager iterations never write.
+                if slot.captured_in_use:
                     raise RuntimeError("DeferredWgrad: this instance already serves a captured step (its frozen job tables are in use); "
                                        "build a new step object for another capture")
-                slot[5] = True
-                dtable = slot[4]
+                slot.captured_in_use = True
+                dtable = slot.captured
                 if self._side is None:
                     self._side = torch.cuda.Stream(device=dev)
                 with torch.cuda.stream(self._side):
-                    dtable.copy_(slot[0], non_blocking=True)
-                    slot[2] = torch.cuda.Event()          # the pinned table may be refilled once this copy has executed
-                    slot[2].record()
+                    dtable.copy_(slot.pinned, non_blocking=True)
+                    slot.copied = torch.cuda.Event()          # the pinned table may be refilled once this copy has executed
+                    slot.copied.record()
             else:
-                dtable = slot[1]
-                dtable.copy_(slot[0], non_blocking=True)
-                slot[2] = torch.cuda.Event()
-                slot[2].record()
+                dtable = slot.eager
+                dtable.copy_(slot.pinned, non_blocking=True)
+                slot.copied = torch.cuda.Event()
+                slot.copied.record()
             nb = _lib.query("ssv_conv1d_bwd_weight_multi_workspace", n, B, Cin, Cout, L, k)
             ws = _ws(nb, dev)
-            max_shift = max(abs(v) for job in jobs for v in job[6])
+            max_shift = max(abs(v) for j in jobs for v in j.shift)
             _lib.call("ssv_conv1d_bwd_weight_multi", _p(dtable), n, dy_bs, x_bs, B, Cin, Cout, L, k, max_shift, n2, nblk, _p(ws), nb, _stream())
         self.jobs = {}
         self.pending.clear()
@@ -332,7 +349,7 @@ class HighwayConvFn(torch.autograd.Function):
             ctx.x_amax = x_amax
             ctx.live = live
             ctx.cfg = (k, dilation, int(causal))
-            ctx.bias_ref = bias           # only its address is used (gradient-arena lookup); not needed by the kernels
+            ctx.bias_ref = bias           # the caller's parameter object (gradient-arena lookup, deferral marks); not needed by the kernels
         return y
 
     @staticmethod
@@ -540,14 +557,14 @@ def _dd_amax(t, cin=None, cout=None):
     return amax_of(t)
 
 
-_INPUT_ONLY = None        # None, or the set of parameter addresses whose gradients the current backward does not want
+_INPUT_ONLY = None        # None, or the set of parameters whose gradients the current backward does not want
 
 
 def _skip_param_grads(*params):
     """True when every given parameter belongs to the module ``input_grads_only`` was entered for."""
     if _INPUT_ONLY is None:
         return False
-    return all(p is not None and p.data_ptr() in _INPUT_ONLY for p in params)
+    return all(p is not None and resident.param_of(p) in _INPUT_ONLY for p in params)
 
 
 @contextlib.contextmanager
@@ -561,8 +578,7 @@ def input_grads_only(module):
     iterations (the critic is the head of its tape): an operator over any OTHER parameter -- a generator layer that adopts ``conv1d_dd``
     / ``channel_ln_dd`` one day -- keeps all of its gradients."""
     global _INPUT_ONLY
-    prev = _INPUT_ONLY
-    _INPUT_ONLY = frozenset(p.data_ptr() for p in module.parameters())
+    prev, _INPUT_ONLY = _INPUT_ONLY, frozenset(module.parameters())
     try:
         yield
     finally:

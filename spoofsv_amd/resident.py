@@ -32,9 +32,17 @@ class _Entry:
         return type(None), ()
 
 
+def param_of(t):
+    """The parameter that tensor ``t`` is, or is a view of: what ``lookup``, ``gradarena`` and ``ops`` hang a parameter's state on and
+    find it by (never by address: another tensor may live there).  Relies on autograd handing a ``Function`` its caller's tensor
+    OBJECTS, in ``forward`` and again from ``ctx.saved_tensors``, and on a view of a view naming the root as its ``_base``; a tensor
+    that merely shares storage (``q.data = p.data``, ``p.detach()``) has no ``_base`` and is nobody's view."""
+    return t if t._base is None else t._base
+
+
 def lookup(w):
     """ctypes pointer to current planes of weight ``w`` (a (Cout, Cin, k) tensor or the packed view of one), or None."""
-    p = w if w._base is None else w._base
+    p = param_of(w)
     e = getattr(p, "_ssv_planes", None)
     if (e is None or e.version != p._version or e.addr != p.data_ptr() or w.data_ptr() != e.addr or e.shape != tuple(w.shape)
             or e.owner() is None):

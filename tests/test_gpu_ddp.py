@@ -35,6 +35,26 @@ def _grads(m):
     return {k: p.grad.detach().cpu().numpy().copy() for k, p in m.named_parameters()}
 
 
+def _count_adopt_copies(arena):
+    """Wrap ``arena.adopt``; the list this returns receives every call's result: the gradients it had to COPY into the arena because
+    the operator that made them found no slot."""
+    moved, adopt = [], arena.adopt
+
+    def counted(params=None):
+        moved.append(adopt(params))
+        return moved[-1]
+    arena.adopt = counted
+    return moved
+
+
+# Gradients that ``GradArena.adopt`` copied into the arena over the two iterations of the tests below -- every other gradient was written
+# into its slot by the kernel that made it.  A replayed step calls no ``adopt`` (its copies are in the graphs), so the count starts when
+# the arena is built: with ``graph`` it is that of the two warm-up iterations and the capture.  Measured on the commit BEFORE slots were
+# found by parameter instead of by address: the lookups must hit and miss exactly as they did.
+_ADOPT_COPIES = {("text2mel", False): 0, ("ssrn", False): 0, ("text2mel", True): 0, ("ssrn", True): 0}
+_ADOPT_COPIES_DEFERRED = {"text2mel": 0, "ssrn": 0}       # (graph=True, seg=True)
+
+
 @pytest.mark.parametrize("kind", ["text2mel", "ssrn"])
 @pytest.mark.parametrize("graph", [False, True])
 def test_segmented_arena_step_is_bit_identical_to_the_plain_step(kind, graph):
@@ -56,6 +76,7 @@ def test_segmented_arena_step_is_bit_identical_to_the_plain_step(kind, graph):
     plain = train.TrainStep(kind, a, oa, batch, gaw, None, graph=False)
     ddp = train.DataParallelRanks(model=b)
     assert ddp.n_buckets == (5 if kind == "text2mel" else 3) and ddp.world == 1
+    moved = _count_adopt_copies(ddp.arena)
     seg = train.TrainStep(kind, b, ob, batch, gaw, ddp, graph=graph).prepare()
     if graph:       # capture ran warm-up iterations on b: start both from the same state again
         b.load_state_dict(a.state_dict())
@@ -75,6 +96,8 @@ def test_segmented_arena_step_is_bit_identical_to_the_plain_step(kind, graph):
         assert torch.equal(p, q), k
     for p in b.parameters():
         assert p.grad.data_ptr() == ddp.arena.slot(p).data_ptr()
+    print("adopt copies", kind, graph, sum(moved), len(moved))
+    assert sum(moved) == _ADOPT_COPIES[kind, graph]          # (the check above also passes when every lookup misses and adopt() copies)
     from spoofsv_amd import tts
     assert b._cut is tts._no_cut
 
@@ -324,6 +347,7 @@ def test_deferred_batched_weight_gradients_match_the_immediate_step(kind, graph,
     oa.refresh_resident_weights(); ob.refresh_resident_weights()
     plain = train.TrainStep(kind, a, oa, batch, gaw, None, graph=False)
     ddp = train.DataParallelRanks(model=b) if seg else None
+    moved = _count_adopt_copies(ddp.arena) if seg else []
     deferred = train.TrainStep(kind, b, ob, batch, gaw, ddp, graph=graph, defer_wgrad=True).prepare()
     if graph:
         b.load_state_dict(a.state_dict())
@@ -342,6 +366,36 @@ def test_deferred_batched_weight_gradients_match_the_immediate_step(kind, graph,
                 assert g is not None and float((p.grad - g).abs().max()) <= 2e-6 * float(p.grad.abs().max()) + 1e-12, k
     for (k, p), q in zip(a.state_dict().items(), b.state_dict().values()):
         assert float((p - q).abs().max()) < 1e-6, k
+    if seg:
+        print("adopt copies deferred", kind, sum(moved), len(moved))
+        assert sum(moved) == _ADOPT_COPIES_DEFERRED[kind]
+
+
+def _dump_train_step_calls():
+    """tools/dump_train_step_calls.py: the recorder of one training iteration's library calls, shared with the tool that wrote the fixture."""
+    import importlib.util
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("dump_train_step_calls", os.path.join(root, "tools", "dump_train_step_calls.py"))
+    tool = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(tool)
+    return tool, os.path.join(root, "tests", "golden", "train_step_calls.json")
+
+
+@pytest.mark.parametrize("kind", ["text2mel", "ssrn"])
+def test_eager_arena_step_issues_the_library_calls_the_committed_record_says(kind):
+    """One eager iteration (after one warm-up) of the step with the gradient arena, the segmented backward and the batched weight
+    gradients: the same library entries in the same order as tests/golden/train_step_calls.json, which was recorded BEFORE gradient
+    slots, deferral marks and ``input_grads_only`` identified a parameter by the tensor instead of by its address.  A weight gradient that
+    is not deferred, or deferred into another launch, shows as another sequence (a gradient that misses its arena slot does not: the
+    copies are counted above); the fixture is never regenerated from a later ops.py."""
+    import json
+    tool, path = _dump_train_step_calls()
+    want = json.load(open(path))
+    assert sorted(want) == ["ssrn", "text2mel"]
+    got = tool.record_step(kind)
+    assert len(got) == len(want[kind]), (len(got), len(want[kind]))
+    for i, (g, w) in enumerate(zip(got, want[kind])):
+        assert g == w, (i, g, w)
 
 
 # ---- RCCL itself, on the one GPU there is: a process group of ONE rank with every collective really issued ------------------

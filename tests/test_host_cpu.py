@@ -439,6 +439,106 @@ def test_grad_arena_dropped_without_release_leaves_no_hooks_and_a_later_backward
     assert len(w._post_accumulate_grad_hooks or {}) == 0
 
 
+def test_grad_arena_slot_belongs_to_the_parameter_not_to_its_address():
+    """A tensor gets a parameter's slot only when it IS that parameter or a dense view of all of it: not a tensor that shares the
+    storage, not a transposed or partial view (whose gradient has another layout or size)."""
+    from spoofsv_amd import gradarena
+    torch.manual_seed(0)
+    p = torch.nn.Parameter(torch.randn(4, 6))
+    ar = gradarena.GradArena([("only", [[p]])])
+    q = torch.nn.Parameter(torch.zeros(4, 6))
+    q.data = p.data
+    assert q.data_ptr() == p.data_ptr() and gradarena.view(q, claim=False) is None
+    assert gradarena.view(p.detach(), claim=False) is None
+    assert gradarena.view(p.t(), claim=False) is None
+    assert gradarena.view(p[1:], claim=False) is None and gradarena.view(p[:1], claim=False) is None
+    assert gradarena.block((q,), 4, 6, claim=False) is None and gradarena.grad_like(p.t()).data_ptr() != ar.slot(p).data_ptr()
+    v = gradarena.view(p.unsqueeze(-1), claim=False)
+    assert v.shape == (4, 6, 1) and v.data_ptr() == ar.slot(p).data_ptr()
+    assert gradarena.view(p.unsqueeze(-1).unsqueeze(0), claim=False).shape == (1, 4, 6, 1)        # a view of a view names the parameter too
+    assert gradarena.view(p, claim=False).data_ptr() == ar.slot(p).data_ptr() and not ar.claimed
+    p.data = p.data.clone()                               # the parameter moved: its gradient's place did not
+    assert gradarena.view(p, claim=False).data_ptr() == ar.slot(p).data_ptr()
+    ar.release()
+    assert gradarena.view(p) is None and not hasattr(p, "_ssv_grad_slot")
+
+
+def test_grad_arena_parameter_pickles_and_deep_copies_without_its_slot():
+    """Python attributes of a Parameter travel with it (torch.save(model), copy.deepcopy(model)); the slot record holds a weak reference,
+    which cannot be pickled: the record reduces to None, and the copy belongs to no arena."""
+    import copy
+    import pickle
+    from spoofsv_amd import gradarena
+    p = torch.nn.Parameter(torch.randn(6))
+    ar = gradarena.GradArena([("only", [[p]])])
+    for q in (pickle.loads(pickle.dumps(p)), copy.deepcopy(p), copy.deepcopy(torch.nn.ParameterList([p]))[0]):
+        assert torch.equal(q, p) and q is not p
+        assert getattr(q, "_ssv_grad_slot", None) is None and gradarena.view(q) is None
+    assert gradarena.view(p, claim=False).data_ptr() == ar.slot(p).data_ptr()
+    ar.release()
+
+
+def test_grad_arena_newest_of_two_arenas_over_a_parameter_owns_the_lookups():
+    from spoofsv_amd import gradarena
+    p = torch.nn.Parameter(torch.randn(6))
+    old = gradarena.GradArena([("only", [[p]])])
+    new = gradarena.GradArena([("only", [[p]])])
+    assert old.slot(p).data_ptr() != new.slot(p).data_ptr()
+    assert gradarena.view(p, claim=False).data_ptr() == new.slot(p).data_ptr()
+    old.release()                                         # changes nothing: the record on p is the newer arena's
+    assert gradarena.view(p, claim=False).data_ptr() == new.slot(p).data_ptr()
+    p.grad = torch.ones(6)
+    assert old.bucket_of(p) == 0 and old.adopt() == 1 and p.grad.data_ptr() == old.slot(p).data_ptr()      # the older one works from its own table
+    p.grad = None
+    new.release()
+    assert gradarena.view(p) is None
+    assert len(p._post_accumulate_grad_hooks or {}) == 0
+
+
+def test_input_grads_only_marks_the_modules_parameters_and_their_views_only():
+    from spoofsv_amd import ops
+    m, other = torch.nn.Linear(6, 8), torch.nn.Linear(6, 8)
+    shares = torch.nn.Parameter(torch.zeros(8, 6))
+    shares.data = m.weight.data
+    assert not ops._skip_param_grads(m.weight)
+    with ops.input_grads_only(m):
+        assert ops._skip_param_grads(m.weight) and ops._skip_param_grads(m.weight, m.bias)
+        assert ops._skip_param_grads(m.weight.unsqueeze(-1)) and ops._skip_param_grads(m.bias.view(1, 8, 1), m.weight)
+        assert not ops._skip_param_grads(other.weight) and not ops._skip_param_grads(m.weight, other.bias)
+        assert shares.data_ptr() == m.weight.data_ptr() and not ops._skip_param_grads(shares)
+        assert not ops._skip_param_grads(m.weight, None)
+        with ops.input_grads_only(other):
+            assert ops._skip_param_grads(other.weight) and not ops._skip_param_grads(m.weight)
+        assert ops._skip_param_grads(m.weight)
+    assert not ops._skip_param_grads(m.weight) and ops._INPUT_ONLY is None
+
+
+def test_deferred_wgrad_refuses_a_parameter_queued_twice_in_one_backward_also_through_a_view():
+    """DeferredWgrad.accepts marks the parameters of a queued job until flush: a second operator over the same parameter -- handed the
+    parameter or a view of it -- is refused loudly.  Host side only (the library's shape predicate): nothing is launched."""
+    import pytest
+    from spoofsv_amd import ops
+    shape = (4, 64, 64, 64, 1)                            # B * L = 256, 64 channels: the batched weight gradient takes it in the default mode
+    w, g = torch.nn.Parameter(torch.randn(64, 64)), torch.nn.Parameter(torch.randn(64))
+    other = torch.nn.Parameter(torch.randn(64, 64))
+    d = ops.DeferredWgrad()
+    with torch.no_grad(), d:
+        for free in (d.flush, d.release_capture):         # (an empty queue: flush launches nothing)
+            assert ops.DeferredWgrad.accepts(*shape, 8, (w.unsqueeze(-1), g, None)) is True
+            assert d.pending == {w, g}
+            assert ops.DeferredWgrad.accepts(*shape, 8, (other.unsqueeze(-1),)) is True
+            for again in ((w,), (w.unsqueeze(-1),), (other, g.view(1, 64))):
+                with pytest.raises(RuntimeError, match="used by two operators of one backward pass"):
+                    ops.DeferredWgrad.accepts(*shape, 8, again)
+            free()
+            assert not d.pending
+        assert ops.DeferredWgrad.accepts(*shape, 8, (w,)) is True
+        d.flush()
+    assert ops._DEFER is None
+    with torch.no_grad():                                  # no instance active: nothing is marked
+        assert ops.DeferredWgrad.accepts(*shape, 8, (w,)) is True and ops.DeferredWgrad.accepts(*shape, 8, (w,)) is True
+
+
 def _segmented_iteration(net, x, y, ddp):
     """forward with cuts, backward segment by segment, each bucket's all-reduce started right after its segment."""
     from spoofsv_amd import train
