@@ -491,6 +491,30 @@ int ssv_power_mel_log(const float* spec, const float* mel, float* out, int R, in
 /* generate_test_utterances.py:135-139 after the trim, on the device: out (B, clip) = y[b][start : start + len] / max(that segment) * peak,
  * len = min(end - start, clip), zeros after; n_out[b] = len.  The maximum, not the absolute maximum, as the reference has it. */
 int ssv_segment_peak(const float* y, const int* bounds, float* out, int* n_out, int B, int n_max, int clip, float peak, ssv_stream_t stream);
+/* The voiced-interval split of GE2E/synthetic_data_preprocess.py:36-47 (`librosa.effects.split(utter, top_db=30)`, every interval
+ * longer than utter_min_len, its first and last tisv_frame frames), in three entries; same codes as above. */
+/* librosa.effects.split(y, top_db) of librosa 0.7.0 (GE2E/synthetic_data_preprocess.py:36-47, the call at :35): frame energies and dB
+ * exactly as ssv_trim_bounds computes them (one device function serves both); every maximal run [f0, f1) of frames above -top_db is the
+ * interval (f0 * hop, min(n_in[b], f1 * hop)), ascending.  intervals (B, K, 2) int, entries from min(count[b], K) on are (0, 0);
+ * count[b] is the number of runs, NOT capped at K (count[b] > K: the caller sees the overflow; nothing is written past entry K).
+ * An empty row gives count 0, a row of exact zeros the one interval (0, n_in[b]).  -2 beyond 8192 frames per row, as ssv_trim_bounds. */
+int ssv_split_intervals(const float* y, const int* n_in, int* intervals, int* count, int B, int n_max, int K, float top_db,
+                        int frame_length, int hop, ssv_stream_t stream);
+/* `for interval in intervals: if (interval[1] - interval[0]) > utter_min_len` (GE2E/synthetic_data_preprocess.py:36-47, the strict
+ * compare at :37) across the rows of a batch, order kept: the spans k < min(count[b], K) of intervals (B, K, 2) are visited in (row,
+ * interval) order; one passes when 0 <= start <= end <= n_max (a span that does not fit is skipped, never followed) and
+ * end - start > min_len.  The passing span of global index g goes to table[g - first] = (row, start, end) for first <= g < first + R;
+ * table (R, 3) int, rows past the last selected span are (-1, 0, 0); total[0] = the number of passing spans overall, whatever first
+ * and R are (total[0] > first + R: run again with a larger first). */
+int ssv_select_spans(const int* intervals, const int* count, int* table, int* total, int B, int K, int n_max, int min_len, int first, int R,
+                     ssv_stream_t stream);
+/* ssv_tisv_frames for the spans of a table (GE2E/synthetic_data_preprocess.py:36-47, the slices of :44-45): fr (2R, n_fft, tisv_frame),
+ * item 2r the first tisv_frame centred frames of seg = y[row][start:end] of table row r (R, 3), item 2r + 1 the last, reflected at the
+ * segment's own ends; valid[r] = 1.  A row of -1, one outside (B, n_max) or one with end - start <= min_len gets zero frames and
+ * valid[r] = 0.  min_len >= max(n_fft / 2, tisv_frame * hop).  A workgroup stages one tile of at most 64 frames of one slice in LDS
+ * and stores whole runs: -2 when (64 - 1) * hop + n_fft > 12288 floats. */
+int ssv_tisv_frames_table(const float* y, const int* table, float* fr, int* valid, int B, int n_max, int R, int n_fft, int hop,
+                          int tisv_frame, int min_len, ssv_stream_t stream);
 
 /* ---- Whole-utterance d-vectors: every frame of every voiced span -> windows -> partition means (additions; ABI version unchanged) ----
  * Replaces GE2E/dvector_create.py:38-73 (`get_STFTs`: `librosa.core.stft` of every concatenated voiced segment, `S[:, j:j+24]` every 12

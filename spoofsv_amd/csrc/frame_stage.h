@@ -1,6 +1,6 @@
 // Framing of centred STFT frames (librosa.stft's reflect padding by N / 2), device side only: the one reflection and the one span clamp
-// every framing kernel uses, and the LDS-staged core of ssv_span_frames (dvector.hip) and ssv_preemph_frames_ragged
-// (corpus_features.hip).  ssv_tisv_frames and ssv_frame_signal are still direct gathers.
+// every framing kernel uses, and the LDS-staged core of ssv_span_frames (dvector.hip), ssv_tisv_frames_table (sv_frontend.hip) and
+// ssv_preemph_frames_ragged (corpus_features.hip).  ssv_tisv_frames and ssv_frame_signal are still direct gathers.
 #pragma once
 
 // index into a row of len samples of position j of the row reflect-padded without repeating its end samples; one reflection:

@@ -71,18 +71,12 @@ __global__ __launch_bounds__(SVF_THREADS) void resample_sinc_kernel(const float*
 // One workgroup per row.  Frame f covers padded samples [f * hop, f * hop + FL) of the row reflect-padded by FL / 2 (zero-padded when
 // the row is no longer than FL / 2); a wave sums one frame's squares in fp32 (lane partial sums in sample order, then the wave tree).
 // dB against the loudest frame and the threshold compare run in double on the <= n / hop + 1 frame energies.
-__global__ __launch_bounds__(SVF_THREADS) void trim_bounds_kernel(const float* __restrict__ y, const int* __restrict__ n_in,
-                                                                  int* __restrict__ bounds, int n_max, double top_db, int FL, int hop) {
-  __shared__ float mse[SVF_TRIM_FRAMES_MAX];
-  __shared__ float redf[SVF_THREADS];
-  __shared__ int redlo[SVF_THREADS], redhi[SVF_THREADS];
-  const int b = blockIdx.x;
-  int n = n_in[b];
-  n = n < 0 ? 0 : (n > n_max ? n_max : n);
-  const float* yb = y + (long)b * n_max;
+
+// The energy stage of trim and split, one arithmetic for both: mse[f] for f < nf = 1 + n / hop (<= SVF_TRIM_FRAMES_MAX, checked on the
+// host against n_max) and, returned, the dB of the loudest frame.  redf: SVF_THREADS floats; ends on a barrier.
+__device__ __forceinline__ double svf_frame_energies(const float* __restrict__ yb, int n, int nf, int FL, int hop, float* mse, float* redf) {
   const int pad = FL / 2;
   const bool reflect = n > pad;
-  const int nf = 1 + n / hop;                           // <= SVF_TRIM_FRAMES_MAX, checked on the host against n_max
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   for (int f = wave; f < nf; f += SVF_THREADS / 64) {
     float acc = 0.f;
@@ -105,11 +99,25 @@ __global__ __launch_bounds__(SVF_THREADS) void trim_bounds_kernel(const float* _
     if ((int)threadIdx.x < s) redf[threadIdx.x] = fmaxf(redf[threadIdx.x], redf[threadIdx.x + s]);
     __syncthreads();
   }
-  const double ref = 10.0 * log10(fmax(1e-10, (double)redf[0]));
+  return 10.0 * log10(fmax(1e-10, (double)redf[0]));
+}
+
+// power_to_db of one frame against the loudest (1e-10 floor, as librosa has it)
+__device__ __forceinline__ double svf_frame_db(float e, double ref) { return 10.0 * log10(fmax(1e-10, (double)e)) - ref; }
+
+__global__ __launch_bounds__(SVF_THREADS) void trim_bounds_kernel(const float* __restrict__ y, const int* __restrict__ n_in,
+                                                                  int* __restrict__ bounds, int n_max, double top_db, int FL, int hop) {
+  __shared__ float mse[SVF_TRIM_FRAMES_MAX];
+  __shared__ float redf[SVF_THREADS];
+  __shared__ int redlo[SVF_THREADS], redhi[SVF_THREADS];
+  const int b = blockIdx.x;
+  int n = n_in[b];
+  n = n < 0 ? 0 : (n > n_max ? n_max : n);
+  const int nf = 1 + n / hop;
+  const double ref = svf_frame_energies(y + (long)b * n_max, n, nf, FL, hop, mse, redf);
   int lo = nf, hi = -1;
   for (int f = threadIdx.x; f < nf; f += SVF_THREADS) {
-    const double db = 10.0 * log10(fmax(1e-10, (double)mse[f])) - ref;
-    if (db > -top_db) { lo = min(lo, f); hi = max(hi, f); }
+    if (svf_frame_db(mse[f], ref) > -top_db) { lo = min(lo, f); hi = max(hi, f); }
   }
   redlo[threadIdx.x] = lo;
   redhi[threadIdx.x] = hi;
@@ -134,6 +142,105 @@ __global__ __launch_bounds__(SVF_THREADS) void trim_bounds_kernel(const float* _
   }
 }
 
+// ---- librosa.effects.split(y, top_db) of librosa 0.7.0 (synthetic_data_preprocess.py:35; host form: vocoder.split_silence) -------------
+// Number of set flags in the threads below this one, and in the whole workgroup (total): a ballot per wave, the waves' counts through
+// wsum (SVF_THREADS / 64 ints of LDS).  Every thread of the workgroup calls it; two barriers, the first keeps a previous call's wsum.
+__device__ __forceinline__ int svf_block_rank(bool flag, int* wsum, int& total) {
+  const unsigned long long m = __ballot(flag);
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  __syncthreads();
+  if (lane == 0) wsum[wave] = __popcll(m);
+  __syncthreads();
+  int below = __popcll(m & ((1ull << lane) - 1ull));
+  total = 0;
+  for (int w = 0; w < SVF_THREADS / 64; ++w) {
+    const int c = wsum[w];
+    if (w < wave) below += c;
+    total += c;
+  }
+  return below;
+}
+
+// One workgroup per row, the energy stage of trim.  Every maximal run [f0, f1) of frames above -top_db is one interval
+// (f0 * hop, min(n, f1 * hop)); the rank of a run is the number of runs that begin before it: a workgroup prefix count over the "a run
+// begins here" flags, SVF_THREADS frames at a time, the count carried from chunk to chunk.  The thread of a run's first frame writes
+// its start, the thread of its last frame its end.  intervals (B, K, 2): runs past K are counted, not stored; entries from
+// min(count, K) on are (0, 0).  An empty row has no run.
+__global__ __launch_bounds__(SVF_THREADS) void split_intervals_kernel(const float* __restrict__ y, const int* __restrict__ n_in,
+                                                                      int* __restrict__ intervals, int* __restrict__ count, int n_max, int K,
+                                                                      double top_db, int FL, int hop) {
+  __shared__ float mse[SVF_TRIM_FRAMES_MAX];               // energies, then flags (1.f: above the threshold)
+  __shared__ float redf[SVF_THREADS];
+  __shared__ int wsum[SVF_THREADS / 64];
+  const int b = blockIdx.x;
+  int n = n_in[b];
+  n = n < 0 ? 0 : (n > n_max ? n_max : n);
+  int* iv = intervals + (long)b * K * 2;
+  int runs = 0;
+  if (n > 0) {                                             // (block-uniform)
+    const int nf = 1 + n / hop;
+    const double ref = svf_frame_energies(y + (long)b * n_max, n, nf, FL, hop, mse, redf);
+    for (int f = threadIdx.x; f < nf; f += SVF_THREADS) mse[f] = svf_frame_db(mse[f], ref) > -top_db ? 1.f : 0.f;   // each thread its own frames
+    __syncthreads();
+    for (int base = 0; base < nf; base += SVF_THREADS) {
+      const int f = base + threadIdx.x;
+      const bool live = f < nf && mse[f] != 0.f;
+      const bool first = live && (f == 0 || mse[f - 1] == 0.f);
+      const bool last = live && (f == nf - 1 || mse[f + 1] == 0.f);
+      int begun;
+      const int before = runs + svf_block_rank(first, wsum, begun);        // runs that begin before frame f
+      const int r = first ? before : before - 1;                             // the run frame f lies in, if it lies in one
+      if (first && r < K) iv[2 * r] = f * hop;
+      if (last && r < K) {
+        const long e = (long)(f + 1) * hop;
+        iv[2 * r + 1] = e < n ? (int)e : n;
+      }
+      runs += begun;
+    }
+  }
+  for (int k = min(runs, K) + threadIdx.x; k < K; k += SVF_THREADS) iv[2 * k] = iv[2 * k + 1] = 0;
+  if (threadIdx.x == 0) count[b] = runs;
+}
+
+// ---- `for interval in intervals: if (interval[1] - interval[0]) > utter_min_len` (synthetic_data_preprocess.py:36-37) across rows --------
+// One workgroup walks the (B, K) spans in (row, interval) order, SVF_THREADS at a time; span k of row b passes when k < min(count[b], K),
+// it fits its row (ssv_clamp_span leaves it as it is) and end - start > min_len.  Its global index g is the prefix count of the passes;
+// table[g - first] = (row, start, end) for first <= g < first + R, the rows after the last one (-1, 0, 0); total[0] = all passes.
+__global__ __launch_bounds__(SVF_THREADS) void select_spans_kernel(const int* __restrict__ intervals, const int* __restrict__ count,
+                                                                   int* __restrict__ table, int* __restrict__ total, int B, int K, int n_max,
+                                                                   int min_len, int first, int R) {
+  __shared__ int wsum[SVF_THREADS / 64];
+  const long n_spans = (long)B * K;                        // < 2^31, checked on the host
+  int passed = 0;
+  for (long base = 0; base < n_spans; base += SVF_THREADS) {
+    const long i = base + threadIdx.x;
+    bool pass = false;
+    int b = 0, start = 0, end = 0;
+    if (i < n_spans) {
+      b = (int)(i / K);
+      start = intervals[2 * i];
+      end = intervals[2 * i + 1];
+      int s = start, e = end;
+      ssv_clamp_span(s, e, n_max);
+      pass = (int)(i % K) < min(count[b], K) && s == start && e == end && end - start > min_len;
+    }
+    int here;
+    const long g = (long)passed + svf_block_rank(pass, wsum, here) - first;
+    if (pass && g >= 0 && g < R) {
+      table[3 * g] = b;
+      table[3 * g + 1] = start;
+      table[3 * g + 2] = end;
+    }
+    passed += here;
+  }
+  const long used = (long)passed - first;
+  for (long r = (used < 0 ? 0 : used) + threadIdx.x; r < R; r += SVF_THREADS) {
+    table[3 * r] = -1;
+    table[3 * r + 1] = table[3 * r + 2] = 0;
+  }
+  if (threadIdx.x == 0) total[0] = passed;
+}
+
 // ---- the framing of librosa.stft(utter, n_fft, hop, win_length) restricted to S[:, :T] and S[:, -T:] (data_preprocess.py:48-60) ----------
 // fr[2b + s][c][t] = reflect_pad(seg, N / 2)[(f0 + t) * hop + c], seg = y[b][start:end], f0 = 0 (s = 0) or 1 + len / hop - T (s = 1);
 // valid[b] = len > min_len (strict, :48), frames of an invalid row are zeros.
@@ -153,6 +260,38 @@ __global__ __launch_bounds__(128) void tisv_frames_kernel(const float* __restric
     v = y[(long)b * n_max + start + ssv_reflect((f0 + t) * hop + c - N / 2, len)];
   }
   fr[((long)blockIdx.z * N + c) * T + t] = v;
+}
+
+// ---- the same two slices for the spans of a table (synthetic_data_preprocess.py:38-45), through the staged core of frame_stage.h -----
+// table (R, 3) int: (row, start, end) as select_spans_kernel writes it.  fr[2r + s][c][t] as above with seg = y[row][start:end].  A
+// workgroup takes one tile of at most SVF_TILE frames of one slice: it stages the samples the tile reads once in LDS and every wave
+// writes whole sample rows as runs of the tile's frames.  A row of -1, one that does not fit the batch or one with
+// end - start <= min_len gets zero frames and valid = 0, and is never followed.
+#define SVF_TILE 64                // frames of a tile: one 256-byte run per sample row and wave store
+#define SVF_TILE_SPAN_MAX 12288    // floats of a tile's staged sample range, (SVF_TILE - 1) * hop + n_fft; 10,592 at hop 160, n_fft 512
+#define SVF_SKEW_SHIFT 5           // ssv_skew's shift: conflict-free at hop = 160 = 5 * 32
+__global__ __launch_bounds__(SVF_THREADS) void tisv_frames_table_kernel(const float* __restrict__ y, const int* __restrict__ table,
+                                                                        float* __restrict__ fr, int* __restrict__ valid, int B, int n_max,
+                                                                        int n_tiles, int N, int hop, int T, int min_len) {
+  __shared__ float sm[SVF_TILE_SPAN_MAX + SVF_TILE_SPAN_MAX / 32 + 1];
+  const int item = blockIdx.x / n_tiles, t0 = (blockIdx.x % n_tiles) * SVF_TILE, r = item >> 1, s = item & 1;
+  const int row = table[3 * r], start = table[3 * r + 1], end = table[3 * r + 2];
+  const int len = end - start;
+  const int cnt = min(SVF_TILE, T - t0);
+  // min_len >= max(N / 2, T * hop), checked on the host: reflect padding and T frames exist (block-uniform)
+  const bool ok = row >= 0 && row < B && start >= 0 && end <= n_max && len > min_len;
+  if (t0 == 0 && s == 0 && threadIdx.x == 0) valid[r] = ok ? 1 : 0;
+  float* dst = fr + (long)item * N * T + t0;
+  if (!ok) {
+    for (int e = threadIdx.x; e < N * cnt; e += SVF_THREADS) dst[(long)(e / cnt) * T + e % cnt] = 0.f;
+    return;
+  }
+  const int f0 = (s ? 1 + len / hop - T : 0) + t0;
+  frame_stage_load<false, SVF_THREADS>(sm, y + (long)row * n_max + start, len, f0 * hop - N / 2, (cnt - 1) * hop + N, SVF_SKEW_SHIFT, 0.f);   // count <= SVF_TILE_SPAN_MAX, checked on the host
+  __syncthreads();
+  const int wave = threadIdx.x >> 6, t = threadIdx.x & 63;
+  if (t >= cnt) return;
+  frame_stage_store(sm, dst + t, T, t * hop, wave, SVF_THREADS / 64, N, SVF_SKEW_SHIFT);
 }
 
 // ---- np.abs(S) ** 2, np.dot(mel_basis, S), np.log10(. + 1e-6)  (data_preprocess.py:50-52), frames-major output ------------------------------
@@ -245,6 +384,43 @@ extern "C" int ssv_tisv_frames(const float* y, const int* bounds, float* fr, int
   hipLaunchKernelGGL(tisv_frames_kernel, dim3(ssv_cdiv(tisv_frame, 128), n_fft, 2 * B), dim3(128), 0, (hipStream_t)stream, y, bounds, fr, valid, n_max,
                      n_fft, hop, tisv_frame, min_len);
   return ssv_check_launch("tisv_frames");
+}
+
+extern "C" int ssv_split_intervals(const float* y, const int* n_in, int* intervals, int* count, int B, int n_max, int K, float top_db,
+                                   int frame_length, int hop, ssv_stream_t stream) {
+  SSV_CHECK(y && n_in && intervals && count && B > 0 && n_max > 0 && K > 0 && frame_length >= 2 && frame_length % 2 == 0 && hop > 0 &&
+            hop <= frame_length && top_db > 0.f, SSV_BAD_SHAPE, "split_intervals: bad argument B=%d n_max=%d K=%d frame_length=%d hop=%d top_db=%g", B, n_max,
+            K, frame_length, hop, (double)top_db);
+  SSV_CHECK(1 + n_max / hop <= SVF_TRIM_FRAMES_MAX, SSV_UNSUPPORTED, "split_intervals: n_max=%d gives %d frames per row (limit %d)", n_max, 1 + n_max / hop,
+            SVF_TRIM_FRAMES_MAX);
+  hipLaunchKernelGGL(split_intervals_kernel, dim3(B), dim3(SVF_THREADS), 0, (hipStream_t)stream, y, n_in, intervals, count, n_max, K, (double)top_db,
+                     frame_length, hop);
+  return ssv_check_launch("split_intervals");
+}
+
+extern "C" int ssv_select_spans(const int* intervals, const int* count, int* table, int* total, int B, int K, int n_max, int min_len, int first, int R,
+                                ssv_stream_t stream) {
+  SSV_CHECK(intervals && count && table && total && B > 0 && K > 0 && n_max > 0 && min_len >= 0 && first >= 0 && R > 0, SSV_BAD_SHAPE,
+            "select_spans: bad argument B=%d K=%d n_max=%d min_len=%d first=%d R=%d", B, K, n_max, min_len, first, R);
+  SSV_CHECK((long)B * K < (1L << 30) && R < (1 << 29), SSV_UNSUPPORTED, "select_spans: B=%d rows of K=%d spans or R=%d table rows exceed the int index range", B, K, R);
+  hipLaunchKernelGGL(select_spans_kernel, dim3(1), dim3(SVF_THREADS), 0, (hipStream_t)stream, intervals, count, table, total, B, K, n_max, min_len, first, R);
+  return ssv_check_launch("select_spans");
+}
+
+extern "C" int ssv_tisv_frames_table(const float* y, const int* table, float* fr, int* valid, int B, int n_max, int R, int n_fft, int hop, int tisv_frame,
+                                     int min_len, ssv_stream_t stream) {
+  SSV_CHECK(y && table && fr && valid && B > 0 && n_max > 0 && R > 0 && n_fft >= 2 && n_fft % 2 == 0 && hop > 0 && hop <= n_fft && tisv_frame > 0,
+            SSV_BAD_SHAPE, "tisv_frames_table: bad argument B=%d n_max=%d R=%d n_fft=%d hop=%d tisv_frame=%d", B, n_max, R, n_fft, hop, tisv_frame);
+  SSV_CHECK(min_len >= n_fft / 2 && (long)min_len >= (long)tisv_frame * hop, SSV_BAD_SHAPE,
+            "tisv_frames_table: min_len=%d must be at least n_fft/2 and tisv_frame*hop (n_fft=%d hop=%d tisv_frame=%d)", min_len, n_fft, hop, tisv_frame);
+  SSV_CHECK((long)(SVF_TILE - 1) * hop + n_fft <= SVF_TILE_SPAN_MAX, SSV_UNSUPPORTED,
+            "tisv_frames_table: a tile of %d frames at hop=%d n_fft=%d reads %ld samples (LDS tile: %d)", SVF_TILE, hop, n_fft,
+            (long)(SVF_TILE - 1) * hop + n_fft, SVF_TILE_SPAN_MAX);
+  const int n_tiles = ssv_cdiv(tisv_frame, SVF_TILE);
+  SSV_CHECK(2L * R * n_tiles < (1L << 31), SSV_UNSUPPORTED, "tisv_frames_table: R=%d table rows of %d tiles exceed the grid", R, n_tiles);
+  hipLaunchKernelGGL(tisv_frames_table_kernel, dim3((unsigned)(2L * R * n_tiles)), dim3(SVF_THREADS), 0, (hipStream_t)stream, y, table, fr, valid, B, n_max,
+                     n_tiles, n_fft, hop, tisv_frame, min_len);
+  return ssv_check_launch("tisv_frames_table");
 }
 
 extern "C" int ssv_power_mel_log(const float* spec, const float* mel, float* out, int R, int F, int T, int nmels, float eps, ssv_stream_t stream) {

@@ -2,7 +2,8 @@
 ``GE2E/data_load.py`` (preprocessed TI-SV data), ``GE2E/train_speech_embedder.py`` (``train``, ``test``,
 ``test_nospoof``: EER and spoof rate).  The embedder and the loss run in libssv_hip.so (``spoofsv_amd.ge2e``); data
 loading, the enrollment/verification bookkeeping and the threshold sweep are host logic, kept as the reference has them.
-``preprocess_tisv`` is ``GE2E/data_preprocess.py`` with its librosa pass on the device (``spoofsv_amd.sv_frontend``), and
+``preprocess_tisv`` is ``GE2E/data_preprocess.py`` with its librosa pass on the device (``spoofsv_amd.sv_frontend``),
+``preprocess_tisv_synthetic`` the same for ``GE2E/synthetic_data_preprocess.py`` (voiced intervals instead of one trimmed span), and
 ``spoof_evaluation`` the in-memory form of ``test`` for features that never touched a disk.
 
 Configuration is a plain dict with the fields of ``GE2E/config/config.yaml`` (``default_config()``), instead of the
@@ -294,6 +295,98 @@ def preprocess_tisv(cfg, speakers, train_spk_num, enroll_num, eval_num, front_en
     return written
 
 
+def _device_interval_slices(fe, max_intervals):
+    """The device pass of ``preprocess_tisv_synthetic``: (y, lengths, rate, names) -> per utterance a (k, 2, tisv_frame, nmels) array.
+    One ``split_call`` per ``capacity`` selected spans; what is read on the host per pass is ``total`` (one integer), then the pass's
+    table and features, and the per-row interval counts once."""
+    def run(y, n, rate, names):
+        B = y.shape[0]
+        capacity = 2 * B
+        per_row = [[] for _ in range(B)]
+        first = 0
+        while True:
+            feats, table, valid, total, count = fe.split_call(y, n, rate, max_intervals=max_intervals, capacity=capacity, first=first)
+            total = int(total.item())
+            if first == 0:
+                for b, c in enumerate(count.cpu().tolist()):
+                    if c > max_intervals:
+                        raise RuntimeError("preprocess_tisv_synthetic: %s has %d voiced intervals, more than max_intervals=%d" % (names[b], c, max_intervals))
+            here = min(capacity, total - first)
+            if here > 0:
+                f, t, v = feats[:here].cpu().numpy(), table[:here].cpu().numpy(), valid[:here].cpu().numpy()
+                for r in range(here):
+                    if v[r]:
+                        per_row[int(t[r, 0])].append(f[r])
+            first += capacity
+            if first >= total:
+                break
+        T, nm = fe.tisv_frame, fe.nmels
+        return [np.stack(p) if p else np.zeros((0, 2, T, nm), dtype=np.float32) for p in per_row]
+    return run
+
+
+def preprocess_tisv_synthetic(cfg, speakers, front_end=None, max_intervals=16):
+    """synthetic_data_preprocess.save_spectrogram_tisv (:13-52) with its librosa pass on the device: no trim, but
+    ``librosa.effects.split(utter, top_db=30)`` (:35), and of every voiced interval longer than ``utter_min_len`` (strict, :37) the first
+    and last ``tisv_frame`` log-mel frames (:44-45).  ``speakers``: ordered {name: value}, a value being
+
+    * a list of wav paths in the caller's order (the reference walks ``os.listdir``, which is not reproducible): every ``.wav`` is
+      taken, there is no 100-file limit and no enrolment fill in this script; or
+    * a device tuple ``(waveforms (U, n) float32, lengths (U,) int32, rate)`` as ``harness.generate_test_utterances(return_waveforms=
+      True)`` returns per speaker (with the TTS sampling rate added), so that synthesized speech never touches the disk.
+
+    One device pass per speaker and sample rate (more when a speaker has more than 2 x utterances selected intervals).  Slices are
+    ordered by file, then interval, then first before last, each stored as (nmels, tisv_frame).  The first ``(len(speakers) // 10) * 8``
+    speakers (:25) are written to ``train_path/speaker<i>.npy``, the others to ``test_path/speaker<i - train>.npy``.  A speaker without
+    any slice is written as an empty ``(0, nmels, tisv_frame)`` float32 array; the reference writes ``np.array([])``, of shape (0,), there
+    -- the one difference, so that the loader's ``utters.shape[0]`` and a later concatenation keep working.  A file with more than
+    ``max_intervals`` voiced intervals raises a ``RuntimeError`` that names it and the count (raise ``max_intervals``); nothing is
+    dropped silently.  Returns the list of written paths.
+    ``front_end(wavs, orig_sr) -> list, per utterance, of (k, 2, tisv_frame, nmels) arrays`` replaces the device pass (tests inject a
+    CPU restatement); an utterance for which it returns more than ``max_intervals`` intervals raises the same error."""
+    d = cfg["data"]
+    os.makedirs(d["train_path"], exist_ok=True)
+    os.makedirs(d["test_path"], exist_ok=True)
+    device_pass = None
+    if front_end is None:
+        from .sv_frontend import TisvFrontEnd
+        fe = TisvFrontEnd.from_config(cfg)
+        device_pass = _device_interval_slices(fe, int(max_intervals))
+    train_spk_num = (len(speakers) // 10) * 8                                  # :25
+    written = []
+    for i, (name, value) in enumerate(speakers.items()):
+        per_utt = {}                                                           # utterance index -> (k, 2, tisv_frame, nmels)
+        if isinstance(value, tuple):
+            if device_pass is None:
+                raise ValueError("preprocess_tisv_synthetic: speaker %r is a device tuple; an injected front_end takes wav paths" % (name,))
+            y, n, rate = value
+            names = ["utterance %d of speaker %r" % (k, name) for k in range(y.shape[0])]
+            per_utt = dict(enumerate(device_pass(y.contiguous(), n.contiguous(), int(rate), names)))
+        else:
+            loaded = [(k, f, read_wav(f)) for k, f in enumerate(value) if f[-4:] == ".wav"]      # :32
+            for rate in sorted({sr for _, _, (sr, _) in loaded}):
+                same = [(k, f, w) for k, f, (sr, w) in loaded if sr == rate]
+                wavs, names = [w for _, _, w in same], [f for _, f, _ in same]
+                if device_pass is not None:
+                    out = device_pass(*pad_batch(wavs, fe.device), rate, names)
+                else:
+                    out = front_end(wavs, rate)
+                    for f, a in zip(names, out):
+                        if len(a) > max_intervals:
+                            raise RuntimeError("preprocess_tisv_synthetic: %s has %d voiced intervals, more than max_intervals=%d" % (f, len(a), max_intervals))
+                for (k, _, _), a in zip(same, out):
+                    per_utt[k] = a
+        utterances_spec = []
+        for k in sorted(per_utt):
+            for a in per_utt[k]:
+                utterances_spec.extend([np.ascontiguousarray(a[0].T), np.ascontiguousarray(a[1].T)])        # :44-45, (nmels, frames)
+        arr = np.array(utterances_spec, dtype=np.float32) if utterances_spec else np.zeros((0, d["nmels"], d["tisv_frame"]), dtype=np.float32)
+        path = os.path.join(d["train_path"], "speaker%d.npy" % i) if i < train_spk_num else os.path.join(d["test_path"], "speaker%d.npy" % (i - train_spk_num))
+        np.save(path, arr)
+        written.append(path)
+    return written
+
+
 @torch.no_grad()
 def spoof_evaluation(cfg, net, enrol, genuine, spoof):
     """The mixture test of ``test`` (train_speech_embedder.py:112-203) on features held in memory: ``enrol`` (N, ke, 2, frames, nmels),
@@ -323,6 +416,10 @@ def dvector_create(cfg, speaker_folders, vad=None, out_dir=".", utterances_per_b
     ``.wav`` files are taken in ``os.listdir`` order, sorted here so that a run can be repeated.  ``vad(path) -> times`` returns what
     ``VAD_chunk`` returns first (VAD_segments.py:130-150; webrtcvad itself is not part of this project); an empty list prints the
     reference's "No voice activity detected" and skips the file.  ``vad=None``: one span per file, its ``trim_bounds(..., 30)``.
+    ``vad="split"``: a file's spans are its ``split_intervals(..., 30)`` intervals, computed on the device and read back once per batch;
+    a file with no interval (an empty one) prints the same message.  That is an ENERGY detector (``librosa.effects.split``: frames
+    within 30 dB of the file's loudest), not webrtcvad: it keeps loud noise, drops quiet speech, and its spans are not cut into 0.4 s
+    chunks -- a device span source where no webrtcvad output is at hand, not a restatement of ``VAD_chunk``.
     Files are decoded by ``read`` (path -> (rate, waveform)), resampled on the device when their rate is not cfg["data"]["sr"], and
     embedded ``utterances_per_batch`` at a time, across files and speakers, in one device pass each.  The embedder is ``net`` or the
     checkpoint cfg["model"]["model_path"].
@@ -333,7 +430,9 @@ def dvector_create(cfg, speaker_folders, vad=None, out_dir=".", utterances_per_b
     left for a file set the reference's ``np.concatenate([])`` raises; here an empty (0, proj) array and an empty id array are written.
     A file none of whose spans gives a window (the reference crashes there, in ``np.stack([])``) contributes no row.  Returns the four paths."""
     from .dvector import DvectorExtractor, spans_from_vad
-    from .sv_frontend import TisvFrontEnd
+    from .sv_frontend import TisvFrontEnd, split_intervals
+    if isinstance(vad, str) and vad != "split":
+        raise ValueError("dvector_create: vad must be None, a callable or 'split', got %r" % (vad,))
     d = cfg["data"]
     fe = TisvFrontEnd.from_config(cfg)
     if net is None:
@@ -360,7 +459,17 @@ def dvector_create(cfg, speaker_folders, vad=None, out_dir=".", utterances_per_b
             y16[j, :m] = y[r, :m]
         n16 = torch.tensor([m for _, _, m in waves], dtype=torch.int32, device=fe.device)
         spans, voiced = None, [True] * len(chunk)
-        if vad is not None:
+        if vad == "split":
+            K = 16
+            while True:                                          # count is not capped: a second pass holds every interval
+                iv, cnt = split_intervals(y16, n16, 30, K)
+                iv, cnt = iv.cpu().tolist(), cnt.cpu().tolist()
+                if max(cnt) <= K:
+                    break
+                K = max(cnt)
+            spans = [[tuple(se) for se in iv[j][:cnt[j]]] for j in range(len(chunk))]
+            voiced = [c > 0 for c in cnt]
+        elif vad is not None:
             spans = []
             for j, k in enumerate(chunk):
                 times = vad(files[k][1])

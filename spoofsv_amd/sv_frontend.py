@@ -10,6 +10,9 @@ Only the 2 x ``tisv_frame`` frames the reference keeps are ever transformed.  Th
 (``ssv_conv1d_fwd``) with a Fourier basis whose 400-sample periodic Hann window is zero-padded to 512 and centred, as librosa does
 for ``win_length < n_fft``.  It runs in exact fp32 (``dft_mode="fp32"``) by default: the features are a LOGARITHM of squared
 magnitudes, which magnifies the split modes' 2e-5-of-the-peak error in quiet bands, and the product is tiny.
+``interval_slices`` / ``split_call`` are the same chain for ``GE2E/synthetic_data_preprocess.py:35-45``, which does not trim but keeps
+the first / last ``tisv_frame`` frames of every interval of ``librosa.effects.split(utter, top_db=30)`` longer than ``utter_min_len``:
+intervals, their selection across rows and the framing from the selected spans stay device tables of static shape.
 There is no CPU fallback: a non-ROCm tensor raises.
 """
 import contextlib
@@ -20,7 +23,8 @@ import torch
 from . import _lib, ops
 from .ops import _p
 from .vocoder import _slaney_mel
-from .wave import KAISER_BEST, Resampler, check_wave, fp32_products, polyphase_bank, rocm_device, sinc_table, trim_bounds  # noqa: F401 (re-exported)
+from .wave import (KAISER_BEST, Resampler, check_wave, fp32_products, polyphase_bank, rocm_device, sinc_table, split_intervals,  # noqa: F401 (re-exported)
+                   trim_bounds)
 
 _F32, _I32 = torch.float32, torch.int32
 
@@ -121,3 +125,45 @@ class TisvFrontEnd:
     def __call__(self, y, lengths, orig_sr):
         y16, n16 = self.resample(y, lengths, orig_sr)
         return self.slices(y16, self.trim_bounds(y16, n16, 30))
+
+    # ------------------------------------------------------------------ voiced intervals (synthetic_data_preprocess.py:35-45)
+    def select_spans(self, intervals, count, n_max, capacity, first=0):
+        """The intervals longer than ``utter_min_len`` of a whole batch, in (row, interval) order: ((capacity, 3) int32 table of
+        (row, start, end) holding the selected spans ``first .. first + capacity - 1``, (-1, 0, 0) after the last; (1,) int32 total)."""
+        B, K, _ = intervals.shape
+        table = torch.empty((int(capacity), 3), dtype=_I32, device=intervals.device)
+        total = torch.empty((1,), dtype=_I32, device=intervals.device)
+        _lib.call("ssv_select_spans", _p(intervals), _p(count), _p(table), _p(total), B, K, int(n_max), self.min_len, int(first), int(capacity),
+                  ops._stream())
+        return table, total
+
+    def frames_table(self, y, table):
+        """((2R, nfft, tisv_frame) frames of the first / last slices of the (R, 3) table's spans, (R,) int32 valid flags)."""
+        B, n_max = y.shape
+        R = table.shape[0]
+        fr = torch.empty((2 * R, self.nfft, self.tisv_frame), dtype=_F32, device=y.device)
+        valid = torch.empty((R,), dtype=_I32, device=y.device)
+        _lib.call("ssv_tisv_frames_table", _p(y), _p(table), _p(fr), _p(valid), B, n_max, R, self.nfft, self.hop_length, self.tisv_frame, self.min_len,
+                  ops._stream())
+        return fr, valid
+
+    def interval_slices(self, y, lengths, top_db=30, max_intervals=16, capacity=None, first=0):
+        """synthetic_data_preprocess.py:35-45 for a ragged batch: ``librosa.effects.split(utter, top_db)`` of every row, every interval
+        longer than ``utter_min_len`` in (row, interval) order, its first and last ``tisv_frame`` log-mel frames.  Returns (features
+        (R, 2, tisv_frame, nmels), table (R, 3) int32 (row, start, end), valid (R,) int32, total (1,) int32, count (B,) int32), all on
+        the device, R = ``capacity`` (default 2 B): the table holds the selected spans ``first .. first + R - 1`` and (-1, 0, 0) with
+        valid = 0 after the last; ``total`` is the number of selected spans of the batch (``total > first + R``: call again with a
+        larger ``first``), ``count[b]`` the number of intervals of row b (``count[b] > max_intervals``: some were not looked at).
+        No length is read on the host and every shape is static."""
+        check_wave(y, lengths, device=self.device)
+        R = 2 * y.shape[0] if capacity is None else int(capacity)
+        intervals, count = split_intervals(y, lengths, top_db, max_intervals)
+        table, total = self.select_spans(intervals, count, y.shape[1], R, first)
+        fr, valid = self.frames_table(y, table)
+        feats = self.mel_log(self.dft(fr))
+        return feats.view(R, 2, self.tisv_frame, self.nmels), table, valid, total, count
+
+    def split_call(self, y, lengths, orig_sr, **kw):
+        """``librosa.load(path, sr)``'s resampling, then ``interval_slices`` (its keywords pass through)."""
+        y16, n16 = self.resample(y, lengths, orig_sr)
+        return self.interval_slices(y16, n16, **kw)

@@ -89,25 +89,45 @@ def _slaney_mel(sr, n_fft, n_mels):
     return fb.astype(np.float32)
 
 
+def _nonsilent_frames(y, top_db, frame_length, hop_length):
+    """``librosa.effects._signal_to_frame_nonsilent`` of librosa 0.7.0 in float64: mean square of the centred frames (reflect padding;
+    zero padding for a signal no longer than half a frame), dB against the loudest frame with a 1e-10 floor, ``> -top_db``.  A boolean
+    per frame; empty when there is no frame."""
+    pad = frame_length // 2
+    yp = np.pad(y.astype(np.float64), pad, mode="reflect") if len(y) > pad else np.pad(y.astype(np.float64), pad, mode="constant")
+    n_frames = 1 + (len(yp) - frame_length) // hop_length
+    if n_frames <= 0:
+        return np.zeros(0, dtype=bool)
+    csum = np.concatenate([[0.0], np.cumsum(yp * yp)])
+    idx = np.arange(n_frames) * hop_length
+    mse = (csum[idx + frame_length] - csum[idx]) / frame_length
+    db = 10.0 * np.log10(np.maximum(1e-10, mse)) - 10.0 * np.log10(max(1e-10, float(mse.max())))
+    return db > -top_db
+
+
 def trim_silence(y, top_db=60.0, frame_length=2048, hop_length=512):
     """Host logic: ``librosa.effects.trim(y, top_db)`` of librosa 0.7.0 for a mono numpy signal -- frame RMS (centred,
     reflect-padded frames), dB relative to the loudest frame, keep from the first to one past the last frame above -top_db.
     Returns (y[start:end], (start, end)).  Runs once per written utterance on ~10^5 samples; not a GPU candidate."""
     y = np.asarray(y)
-    pad = frame_length // 2
-    yp = np.pad(y.astype(np.float64), pad, mode="reflect") if len(y) > pad else np.pad(y.astype(np.float64), pad, mode="constant")
-    n_frames = 1 + (len(yp) - frame_length) // hop_length
-    if n_frames <= 0:
-        return y[0:0], (0, 0)
-    csum = np.concatenate([[0.0], np.cumsum(yp * yp)])
-    idx = np.arange(n_frames) * hop_length
-    mse = (csum[idx + frame_length] - csum[idx]) / frame_length
-    db = 10.0 * np.log10(np.maximum(1e-10, mse)) - 10.0 * np.log10(max(1e-10, float(mse.max())))
-    nz = np.flatnonzero(db > -top_db)
+    nz = np.flatnonzero(_nonsilent_frames(y, top_db, frame_length, hop_length))
     if nz.size == 0:
         return y[0:0], (0, 0)
     start, end = int(nz[0]) * hop_length, min(len(y), (int(nz[-1]) + 1) * hop_length)
     return y[start:end], (start, end)
+
+
+def split_silence(y, top_db=60.0, frame_length=2048, hop_length=512):
+    """Host logic: ``librosa.effects.split(y, top_db)`` of librosa 0.7.0 for a mono numpy signal -- the frames of ``trim_silence``;
+    every maximal run [f0, f1) of frames above -top_db is one interval (f0 * hop_length, min(len(y), f1 * hop_length)).  Returns an
+    (n, 2) int array in ascending order, (0, 2) for an empty signal; its first start and last end are ``trim_silence``'s bounds.
+    The device form for ragged batches is ``wave.split_intervals``."""
+    y = np.asarray(y)
+    if len(y) == 0:
+        return np.zeros((0, 2), dtype=np.int64)
+    ns = _nonsilent_frames(y, top_db, frame_length, hop_length).astype(np.int8)
+    edges = np.flatnonzero(np.diff(np.concatenate([[0], ns, [0]])))          # run starts and one-past-ends, alternating
+    return np.minimum(edges * hop_length, len(y)).reshape(-1, 2).astype(np.int64)
 
 
 class Vocoder:

@@ -1,7 +1,7 @@
 """The waveform stages every GPU front end shares (``sv_frontend``, ``dvector``, ``corpus_features``): the argument check of a ragged
 ``(B, n_max)`` float32 batch with int32 device lengths or bounds, the device lookup of a constructor, resampy's ``kaiser_best``
-resampling (``ssv_resample_sinc`` and its polyphase filter banks), ``librosa.effects.trim``'s bounds (``ssv_trim_bounds``) and the
-switch to exact fp32 for one product.  There is no CPU fallback: a non-ROCm tensor raises.
+resampling (``ssv_resample_sinc`` and its polyphase filter banks), ``librosa.effects.trim``'s bounds (``ssv_trim_bounds``),
+``librosa.effects.split``'s intervals (``ssv_split_intervals``) and the switch to exact fp32 for one product.  There is no CPU fallback: a non-ROCm tensor raises.
 """
 import contextlib
 from fractions import Fraction
@@ -153,3 +153,18 @@ def trim_bounds(y, lengths, top_db=30.0, frame_length=2048, hop_length=512, out=
     bounds = out if out is not None else torch.empty((B, 2), dtype=_I32, device=y.device)
     _lib.call("ssv_trim_bounds", _p(y), _p(lengths), _p(bounds), B, n_max, float(top_db), int(frame_length), int(hop_length), ops._stream())
     return bounds
+
+
+def split_intervals(y, lengths, top_db=30.0, max_intervals=16, frame_length=2048, hop_length=512):
+    """``librosa.effects.split(y, top_db)`` intervals of every row (the device form of ``vocoder.split_silence``): ((B, max_intervals, 2)
+    int32 (start, end) pairs in ascending order, (0, 0) from ``min(count, max_intervals)`` on; (B,) int32 count).  ``count`` is the true
+    number of intervals of a row: ``count > max_intervals`` tells the caller that some were not stored.  The frame energies are those
+    of ``trim_bounds``, so a row's first start and last end are its trim bounds."""
+    check_wave(y, lengths)
+    B, n_max = y.shape
+    K = int(max_intervals)
+    intervals = torch.empty((B, K, 2), dtype=_I32, device=y.device)
+    count = torch.empty((B,), dtype=_I32, device=y.device)
+    _lib.call("ssv_split_intervals", _p(y), _p(lengths), _p(intervals), _p(count), B, n_max, K, float(top_db), int(frame_length), int(hop_length),
+              ops._stream())
+    return intervals, count
