@@ -401,6 +401,35 @@ size_t ssv_ge2e_loss_bwd_workspace(int N, int M, int D);
 int ssv_ge2e_loss_bwd(const float* emb, const float* w, const float* b, const float* dloss, float* demb, float* dw, float* db,
                       int N, int M, int D, void* ws, size_t ws_bytes, ssv_stream_t stream);
 
+/* GE2E training on a corpus held on the device: the batch assembly and the tail of one iteration.
+ *
+ * Replaces SpeakerDatasetTIMITPreprocessed.__getitem__, GE2E/data_load.py:77-85 (`utters[utter_index]`, `np.transpose(.., (0,2,1))`,
+ * then the DataLoader's stack and upload), for a whole batch: corpus (U_total, nmels, frames) holds every speaker's utterances,
+ * rows (Bn = N*M int32, DEVICE) the batch's global utterance rows, out (Bn, frames, nmels) is what ssv_lstm_train_fwd takes:
+ * out[b][t][f] = corpus[rows[b]][f][t].  Rows may repeat (np.random.randint draws with replacement).  The table is not read on
+ * the host: the caller, who drew it, validates it before the upload.  A row outside [0, U_total) is never dereferenced; its
+ * utterance is written as NaN.  Any (nmels, frames): the transpose is tiled. */
+int ssv_tisv_batch_gather(const float* corpus, long U_total, const int* rows, float* out, int Bn, int nmels, int frames, ssv_stream_t stream);
+/* Replaces clip_grad_norm_(embedder_net.parameters(), 3.0), clip_grad_norm_(ge2e_loss.parameters(), 1.0) and
+ * optimizer.step() (optim.SGD), GE2E/train_speech_embedder.py:84-86, for all parameters in two launches.  `chunks` is a DEVICE array
+ * of contiguous pieces of parameters (any n >= 1) with their clipping group, 0 <= group < ngroups <= SSV_CLIP_SGD_MAX_GROUPS;
+ * max_norm is a HOST array of ngroups floats, read during the call.  Per group: S = sum g^2 in double (one partial per piece, added
+ * in piece order), norms[group] = sqrt(S) (DEVICE floats, ngroups of them: what clip_grad_norm_ returns),
+ * coef = min(1, max_norm / (sqrt(S) + 1e-6)) in double, rounded once to float, step = lr * coef in float, p <- p - step * g
+ * (product and difference each rounded once).  No atomics and no arrival order anywhere: the same inputs give the same bits.  A
+ * non-finite gradient propagates as with error_if_nonfinite=False.
+ * DIFFERENCE from the reference: the gradients are NOT rescaled in memory (clip_grad_norm_ multiplies them by coef in place; nothing
+ * reads them before the next zero_grad()).
+ * loss, loss_hist, hist_len, step_dev (DEVICE, optional): loss_hist[*step_dev % hist_len] = *loss and *step_dev += 1, inside the second
+ * launch, so that a replayed hipGraph fills successive slots and the host reads losses back when it wants them (the step_dev
+ * convention of ssv_adam_multi).  step_dev alone counts the calls.  ws: ssv_clip_sgd_workspace(nchunks) bytes (a long, like the n of
+ * the tables: one double per piece). */
+#define SSV_CLIP_SGD_MAX_GROUPS 8
+typedef struct { float* p; const float* g; long n; int group; int pad_; } ssv_clip_sgd_chunk;
+long ssv_clip_sgd_workspace(int nchunks);
+int ssv_clip_sgd_multi(const ssv_clip_sgd_chunk* chunks, int nchunks, const float* max_norm, int ngroups, float lr, float* norms,
+                       const float* loss, float* loss_hist, int hist_len, int* step_dev, void* ws, size_t ws_bytes, ssv_stream_t stream);
+
 /* ---- Vocoder and spectrogram front end ------------------------------------------------
  * Replaces the CPU tail of synthesis, synthesize.py:138-147 / generate_test_utterances.py:128-139
  * (`librosa.core.griffinlim(S, n_iter=64, hop_length, win_length)`, `signal.lfilter([1], [1, -PREEMPH], y)`, peak

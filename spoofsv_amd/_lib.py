@@ -21,6 +21,11 @@ class AdamChunk(ctypes.Structure):
                 ("v", ctypes.c_void_p), ("n", ctypes.c_long)]
 
 
+class ClipSgdChunk(ctypes.Structure):
+    """Mirror of ``ssv_clip_sgd_chunk``."""
+    _fields_ = [("p", ctypes.c_void_p), ("g", ctypes.c_void_p), ("n", ctypes.c_long), ("group", ctypes.c_int), ("pad_", ctypes.c_int)]
+
+
 class PackJob(ctypes.Structure):
     """Mirror of ``ssv_pack_job``."""
     _fields_ = [("w", ctypes.c_void_p), ("planes", ctypes.c_void_p), ("M", ctypes.c_int), ("K", ctypes.c_int),

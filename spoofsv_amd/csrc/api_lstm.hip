@@ -101,8 +101,8 @@ int lstm_fwd_wave(const float* x, const float* const* w_ih, const float* const* 
   // rows, split weight planes, the weights' scale (ssv_lstm_fwd_cached: d-vector extraction runs batch after batch on fixed weights; the six
   // absmax scans over 48 MB of weights and the six packs were ~0.35 ms of an 11.6 ms forward)
   for (int l = 0; !packed && l < layers; ++l) {                   // biases side by side: [layer][b_ih (4H) | b_hh (4H)]
-    SSV_HIP(hipMemcpyAsync(bias + (long)l * 8 * H, b_ih[l], (size_t)4 * H * sizeof(float), hipMemcpyDeviceToDevice, st));
-    SSV_HIP(hipMemcpyAsync(bias + (long)l * 8 * H + 4 * H, b_hh[l], (size_t)4 * H * sizeof(float), hipMemcpyDeviceToDevice, st));
+    SSV_TRY(ssv_copy_rows(b_ih[l], 0, bias + (long)l * 8 * H, 0, 1, (long)4 * H, st));
+    SSV_TRY(ssv_copy_rows(b_hh[l], 0, bias + (long)l * 8 * H + 4 * H, 0, 1, (long)4 * H, st));
   }
   // weights, rows gate-interleaved (row 4u + gate) so that the product can finish the cell in its epilogue
   unsigned short* ih0_hi = ws_u16(base, s.ih0);
@@ -115,7 +115,7 @@ int lstm_fwd_wave(const float* x, const float* const* w_ih, const float* const* 
   if (f16) {
     const int npb = 64 / (2 * layers);                            // partial maxima per weight matrix
     if (!packed) {
-      SSV_HIP(hipMemsetAsync(aux, 0, LSTM_AUX_FLOATS * sizeof(float), st));
+      SSV_TRY(ssv_launch_fill(aux, 0.f, LSTM_AUX_FLOATS, st));      // (a kernel, not a memset node: see ssv_lstm_bwd)
       for (int l = 0; l < layers; ++l) {
         SSV_TRY(ssv_launch_absmax(w_ih[l], 0, 1, (long)4 * H * (l == 0 ? F : H), aux + (2 * l) * npb, npb, st));
         SSV_TRY(ssv_launch_absmax(w_hh[l], 0, 1, (long)4 * H * H, aux + (2 * l + 1) * npb, npb, st));
@@ -163,7 +163,7 @@ int lstm_fwd_wave(const float* x, const float* const* w_ih, const float* const* 
   // layers above it (K = 2 H) as entry 0.  Before, a step was two launches -- 336 workgroups with 24 chunks, then 672 with 48 -- each with a
   // half-empty last round; together they are 1008 workgroups = two full rounds of 512.  SSV_LSTM_MERGE=0 keeps the two launches (tuning).
   if (presplit) {
-    SSV_HIP(hipMemsetAsync(base + s.hp, 0, (size_t)layers * 2 * 2 * s.hp_plane, st));
+    SSV_TRY(ssv_launch_fill((float*)(base + s.hp), 0.f, (long)((size_t)layers * s.hp_plane), st));      // layers * 2 * 2 * hp_plane bytes
     g.hs_planes = ws_u16(base, s.hp); g.hs_plane_bytes = (long)s.hp_plane; g.hs_npad = s.npad;
   }
   for (int step = 0; merge && layers >= 2 && step < T + layers - 1; ++step) {

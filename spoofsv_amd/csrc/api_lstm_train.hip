@@ -163,7 +163,9 @@ extern "C" int ssv_lstm_bwd(const float* dh_last, const void* saved, const float
   const size_t rows_h = (size_t)(H / 16) * (4 * H / 32) * 512;               // elements of the first H rows of a [2H x 4H] plane
   if (f16) {                                                                 // the weights' partial maxima: W_ih[l >= 1] and W_hh[l] (layer 0's W_ih half is zero)
     const int npb = 64 / (2 * layers);
-    SSV_HIP(hipMemsetAsync(aux, 0, 64 * sizeof(float), st));
+    // (zeroed by a kernel, as everything below that clears memory: a memset NODE of a captured iteration was seen to run out of order with the kernels around
+    // it on the first replay of a process -- the maxima cleared after they were written, the planes split with a zero scale, layer 0's gradients zero)
+    SSV_TRY(ssv_launch_fill(aux, 0.f, 64, st));
     for (int l = 0; l < layers; ++l) {
       if (l > 0) SSV_TRY(ssv_launch_absmax(w_ih[l], 0, 1, (long)4 * H * H, aux + (2 * l) * npb, npb, st));
       SSV_TRY(ssv_launch_absmax(w_hh[l], 0, 1, (long)4 * H * H, aux + (2 * l + 1) * npb, npb, st));
@@ -177,8 +179,8 @@ extern "C" int ssv_lstm_bwd(const float* dh_last, const void* saved, const float
     unsigned short* hi = ws_u16(base, s.wta + (size_t)l * s.wta_stride);
     unsigned short* lo = (unsigned short*)((char*)hi + split_bytes(2 * H, 4 * H, 1));
     if (l == 0) {                                                            // no data gradient of the utterance itself: zero rows (mostly skipped, see skip_rows)
-      SSV_HIP(hipMemsetAsync(hi, 0, rows_h * sizeof(unsigned short), st));
-      SSV_HIP(hipMemsetAsync(lo, 0, rows_h * sizeof(unsigned short), st));
+      SSV_TRY(ssv_launch_fill((float*)hi, 0.f, (long)(rows_h / 2), st));           // rows_h is a multiple of 512 elements
+      SSV_TRY(ssv_launch_fill((float*)lo, 0.f, (long)(rows_h / 2), st));
     } else SSV_TRY(pack_t(w_ih[l], hi, lo));
     SSV_TRY(pack_t(w_hh[l], hi + rows_h, lo + rows_h));
   }
@@ -220,7 +222,7 @@ extern "C" int ssv_lstm_bwd(const float* dh_last, const void* saved, const float
     if (T > 1) SSV_TRY(lstm_weight_grad(dg + 4 * HN, 4 * HN, hs + (long)l * T * HN, HN, dw_hh[l], 4 * H, H, Bn, T - 1, base + s.slabs, st, f32, f16 ? &al : nullptr, &hl));
     else SSV_TRY(ssv_launch_fill(dw_hh[l], 0.f, (long)4 * H * H, st));
     SSV_TRY(ssv_launch_reduce_slabs(rs + (long)l * T * 4 * H, db_ih[l], 4 * H, T, 4 * H, st));      // sum over frames of sum_b dgates[l][t][r][b] (the cell kernel's row sums)
-    SSV_HIP(hipMemcpyAsync(db_hh[l], db_ih[l], (size_t)4 * H * sizeof(float), hipMemcpyDeviceToDevice, st));
+    SSV_TRY(ssv_copy_rows(db_ih[l], 0, db_hh[l], 0, 1, (long)4 * H, st));
   }
   return 0;
 }

@@ -4,7 +4,8 @@
 loading, the enrollment/verification bookkeeping and the threshold sweep are host logic, kept as the reference has them.
 ``preprocess_tisv`` is ``GE2E/data_preprocess.py`` with its librosa pass on the device (``spoofsv_amd.sv_frontend``),
 ``preprocess_tisv_synthetic`` the same for ``GE2E/synthetic_data_preprocess.py`` (voiced intervals instead of one trimmed span), and
-``spoof_evaluation`` the in-memory form of ``test`` for features that never touched a disk.
+``spoof_evaluation`` the in-memory form of ``test`` for features that never touched a disk.  ``ResidentSpeakerCorpus`` holds the
+training corpus on the device and draws the loader's batches as row tables (``train`` with ``cfg["train"]["resident"]``).
 
 Configuration is a plain dict with the fields of ``GE2E/config/config.yaml`` (``default_config()``), instead of the
 reference's module-global ``hparam`` object.
@@ -17,7 +18,7 @@ import numpy as np
 import torch
 from torch.utils.data import DataLoader, Dataset
 
-from .ge2e import GE2ELoss, SpeechEmbedder, train_iteration
+from .ge2e import GE2ELoss, GE2ETrainStep, SpeechEmbedder, tisv_batch_gather, train_iteration
 
 
 def default_config():
@@ -55,13 +56,159 @@ class SpeakerDatasetPreprocessed(Dataset):
         return torch.tensor(np.transpose(utterance, axes=(0, 2, 1)))
 
 
+def _npy_shape(path):
+    """Shape of the array in a ``.npy`` file, from its header alone."""
+    fmt = np.lib.format
+    with open(path, "rb") as f:
+        major = fmt.read_magic(f)[0]
+        return tuple((fmt.read_array_header_1_0 if major == 1 else fmt.read_array_header_2_0)(f)[0])
+
+
+class _SpeakerRows(Dataset):
+    """The index-only twin of ``SpeakerDatasetPreprocessed(path, M, shuffle=True)``: item ``idx`` makes the ONE random call the host dataset
+    makes (data_load.py:77) and returns the speaker's M global utterance rows.  No file is opened."""
+
+    def __init__(self, offsets, counts, utter_num):
+        self.offsets, self.counts, self.utter_num = offsets, counts, utter_num
+
+    def __len__(self):
+        return len(self.counts)
+
+    def __getitem__(self, idx):
+        return torch.from_numpy(self.offsets[idx] + np.random.randint(0, self.counts[idx], self.utter_num))
+
+
+class _RowBatches:
+    """One ``DataLoader`` over ``_SpeakerRows``; every ``iter()`` is an epoch of (N*M,) int32 row tables."""
+
+    def __init__(self, loader):
+        self.loader = loader
+
+    def __len__(self):
+        return len(self.loader)
+
+    def __iter__(self):
+        for rows in self.loader:
+            yield rows.reshape(-1).to(torch.int32)
+
+
+class ResidentSpeakerCorpus:
+    """The preprocessed TI-SV corpus of ``SpeakerDatasetPreprocessed`` (one ``.npy`` (utterances, nmels, frames) per speaker, read in
+    ``sorted(os.listdir(path))`` order, the list the host dataset indexes) as ONE float32 tensor ``data`` (U_total, nmels, frames) on
+    ``device``, every speaker's utterances contiguous from ``offsets[s]``, ``counts[s]`` of them.  Read once; the training loop then
+    needs neither the disk nor the host's copies (data_load.py:75-85 per item of every batch).
+
+    ``bytes`` (4 * U_total * nmels * frames) is known from the files' headers before anything is allocated; a corpus that does not fit
+    the device's free memory raises a ``RuntimeError`` naming the figure.  A speaker file without utterances (the host loader crashes
+    there, in ``randint(0, 0)``) or with another (nmels, frames) than the first raises a ``ValueError`` naming the file.
+    ``device`` may be the CPU: the index logic (``batches``) needs no device; ``gather`` does."""
+
+    def __init__(self, path, device):
+        self.path, self.device = path, torch.device(device)
+        self.file_list = sorted(os.listdir(path))
+        if not self.file_list:
+            raise ValueError("ResidentSpeakerCorpus: no speaker files under %s" % path)
+        shapes = []
+        for name in self.file_list:
+            shape = _npy_shape(os.path.join(path, name))
+            if len(shape) != 3 or shape[0] < 1:
+                raise ValueError("ResidentSpeakerCorpus: %s holds no utterances (shape %s); every speaker file must be (utterances >= 1, nmels, frames)"
+                                 % (os.path.join(path, name), tuple(shape)))
+            if shapes and tuple(shape[1:]) != tuple(shapes[0][1:]):
+                raise ValueError("ResidentSpeakerCorpus: %s holds (nmels, frames) = %s, the corpus %s" % (os.path.join(path, name), tuple(shape[1:]), tuple(shapes[0][1:])))
+            shapes.append(shape)
+        self.counts = np.array([s[0] for s in shapes], dtype=np.int64)
+        self.offsets = np.concatenate([[0], np.cumsum(self.counts)[:-1]]).astype(np.int64)
+        self.nmels, self.frames = int(shapes[0][1]), int(shapes[0][2])
+        self.total = int(self.counts.sum())
+        self.bytes = 4 * self.total * self.nmels * self.frames
+        if self.device.type == "cuda":
+            free = torch.cuda.mem_get_info(self.device)[0] + torch.cuda.memory_reserved(self.device) - torch.cuda.memory_allocated(self.device)
+            if self.bytes > free:
+                raise RuntimeError("ResidentSpeakerCorpus(%s): %d utterances of (%d, %d) need %d bytes of device memory (%.1f GB), %d are free: "
+                                   "train from the host loader instead" % (path, self.total, self.nmels, self.frames, self.bytes, self.bytes / 2.0 ** 30, free))
+        self.data = torch.empty((self.total, self.nmels, self.frames), dtype=torch.float32, device=self.device)
+        for name, off, cnt in zip(self.file_list, self.offsets, self.counts):            # one speaker at a time: no second host copy of the corpus
+            utters = np.ascontiguousarray(np.load(os.path.join(path, name)), dtype=np.float32)
+            self.data[off:off + cnt].copy_(torch.from_numpy(utters))
+
+    def __len__(self):
+        return len(self.file_list)
+
+    def batches(self, N, M):
+        """The row tables of ``DataLoader(SpeakerDatasetPreprocessed(path, M, shuffle=True), batch_size=N, shuffle=True, drop_last=True)``,
+        with exactly its random stream: a real ``DataLoader`` with the same arguments (``num_workers=0``) over ``_SpeakerRows``, so the same
+        ``torch`` / ``numpy`` seeds select the same speakers and utterances.  Every ``iter()`` of the result is one epoch; an item is the
+        batch's (N*M,) int32 table of global utterance rows, speaker after speaker."""
+        return _RowBatches(DataLoader(_SpeakerRows(self.offsets, self.counts, M), batch_size=N, shuffle=True, num_workers=0, drop_last=True))
+
+    def gather(self, rows_dev, out):
+        """``out[b, t, f] = data[rows_dev[b], f, t]`` on the device (``ssv_tisv_batch_gather``)."""
+        return tisv_batch_gather(self.data, rows_dev, out)
+
+
 def _embedder(cfg, device):
     m = cfg["model"]
     return SpeechEmbedder(cfg["data"]["nmels"], m["hidden"], m["num_layer"], m["proj"]).to(device)
 
 
+def _train_resident(cfg, model_path=None):
+    """``train`` on a corpus held on the device: ``ResidentSpeakerCorpus`` draws the loader's batches as row tables, ``GE2ETrainStep`` runs
+    the iteration (replayed unless cfg["train"]["graph"] is False).  The loss is not read back per iteration: the step keeps a history on
+    the device, read at every ``log_interval`` and at the end of an epoch.  Same log lines, checkpoints and returned history as ``train``."""
+    device = torch.device(cfg["device"])
+    tr = cfg["train"]
+    corpus = ResidentSpeakerCorpus(cfg["data"]["train_path"], device)
+    batches = corpus.batches(tr["N"], tr["M"])
+    net = _embedder(cfg, device)
+    if tr["restore"]:
+        net.load_state_dict(torch.load(model_path, map_location="cpu"))
+    ge2e_loss = GE2ELoss(device)
+    if tr["checkpoint_dir"]:
+        os.makedirs(tr["checkpoint_dir"], exist_ok=True)
+    net.train()
+    step = GE2ETrainStep(net, ge2e_loss, tr["N"], tr["M"], corpus.frames, tr["lr"], graph=tr.get("graph", True), corpus=corpus,
+                         hist_len=max(1, tr["log_interval"]))
+    step.prepare()
+    iteration, history = 0, []
+    e = batch_id = 0
+    for e in range(tr["epochs"]):
+        total, pending = 0.0, 0
+
+        def drain():
+            nonlocal total, pending
+            for v in step.losses(pending):
+                history.append(v)
+                total += v
+            pending = 0
+        for batch_id, rows in enumerate(batches):
+            step.run(rows)
+            pending += 1
+            iteration += 1
+            if (batch_id + 1) % tr["log_interval"] == 0:
+                drain()
+                mesg = "{0}\tEpoch:{1}[{2}/{3}],Iteration:{4}\tLoss:{5:.4f}\tTLoss:{6:.4f}\t\n".format(
+                    time.ctime(), e + 1, batch_id + 1, len(corpus) // tr["N"], iteration, history[-1], total / (batch_id + 1))
+                print(mesg)
+                if tr["log_file"]:
+                    with open(tr["log_file"], "a") as f:
+                        f.write(mesg)
+        drain()
+        if tr["checkpoint_dir"] and (e + 1) % tr["checkpoint_interval"] == 0:
+            torch.save({k: v.cpu() for k, v in net.state_dict().items()},
+                       os.path.join(tr["checkpoint_dir"], "ckpt_epoch_%d_batch_id_%d.pth" % (e + 1, batch_id + 1)))
+    if tr["checkpoint_dir"]:
+        torch.save({k: v.cpu() for k, v in net.state_dict().items()},
+                   os.path.join(tr["checkpoint_dir"], "final_epoch_%d_batch_id_%d.model" % (e + 1, batch_id + 1)))
+    return net, history
+
+
 def train(cfg, model_path=None):
-    """train_speech_embedder.py:40-108.  Returns (embedder, list of per-iteration losses)."""
+    """train_speech_embedder.py:40-108.  Returns (embedder, list of per-iteration losses).  cfg["train"]["resident"] = True (absent by
+    default) trains from a corpus held on the device instead of the host loader (``_train_resident``; cfg["train"]["graph"], default True
+    there, selects replay)."""
+    if cfg["train"].get("resident", False):
+        return _train_resident(cfg, model_path)
     device = torch.device(cfg["device"])
     tr = cfg["train"]
     loader = DataLoader(SpeakerDatasetPreprocessed(cfg["data"]["train_path"], tr["M"], shuffle=True), batch_size=tr["N"], shuffle=True,
