@@ -254,6 +254,7 @@ int ssv_attention_step(const float* k, long kv_bs, const float* q_last, long q_b
                        int B, int d, int N, ssv_stream_t stream);
 /* col_dev (DEVICE int*, may be NULL): when given, the frame index is *col_dev instead of `col` and q_last must point at
  * column 0 of Q -- one captured hipGraph of a fixed-shape synthesis step can then be replayed for every frame.
+ * With col_dev the frame index is NOT range-checked, on the host or in the kernel: the caller must keep *col_dev below a_T.
  * ssv_synth_advance closes such a step: mel_in[b][f][*col_dev + 1] = y[b][f][*col_dev] (both (B,F,T) dense; the frame just
  * synthesised is the next input, synthesize.py:108-109), then *col_dev += 1. */
 int ssv_synth_advance(const float* y, float* mel_in, int* col_dev, int B, int F, int T, ssv_stream_t stream);
