@@ -595,6 +595,27 @@ int ssv_corpus_normalize_pack(const float* lin, const float* mel, const float* m
                               float* mel_out, float* lin_out, int* rt, int B, int F, int M, int T_max, int RT_max, int r, int log_feature,
                               float power, float ref_db, float max_db, ssv_stream_t stream);
 
+/* ---- Text2Mel / SSRN batches from a spectrogram corpus held on the device (additions; ABI version unchanged) ----------------------
+ * Replaces VCTKDataset.__getitem__, data/dataset.py:83-173 (`np.load` of the cached `_mel.npy` / `_lin.npy`, the text ids, the speaker
+ * code, per item of every batch) and collate_pad_2 / collate_pad_3, data/dataset.py:187-258 (zero padding to the batch's longest item,
+ * the stack, then the upload), for a whole batch in one launch per tensor.  The corpus lives in ragged arenas: item i is a
+ * contiguous block at arena + off[i] (off: n_items int64, in ELEMENTS; len: n_items int32; both on the DEVICE).  rows (n_rows int32,
+ * DEVICE) is the whole epoch's item order, uploaded once; a batch is its entries [row0, row0 + B), row0 a host integer.  Nothing is
+ * read on the host.  An entry outside [0, n_items), a negative len, or a block that does not lie inside the arena_n elements of the
+ * arena is never dereferenced: that item of the batch is written as NaN (ids: -1) and nothing else changes.
+ * Codes: NULL pointers, non-positive sizes, [row0, row0 + B) outside the table, out_bs < F * width: -1; a grid that does not fit: -2. */
+/* Item i is a row-major (F, len[i]) float block.  out[b * out_bs + f * width + t] = t < len[r] ? arena[off[r] + f * len[r] + t] : 0 for
+ * b < B, f < F, t < width, r = rows[row0 + b]: width may exceed the batch's longest item (zeros after it) or fall below it (the item is
+ * clipped); out_bs is the batch stride in elements.  Any len >= 0 and any off: 16-byte accesses where a row starts on a 16-byte
+ * boundary on both sides, 4-byte ones elsewhere.  The speaker codes (B, D, 1) are this entry with F = 1, len = width = D over the
+ * (n_speakers, D) table, off[i] = D * speaker(i). */
+int ssv_corpus_gather(const float* arena, long arena_n, const long* off, const int* len, int n_items, const int* rows, long n_rows,
+                      long row0, float* out, int B, int F, int width, long out_bs, ssv_stream_t stream);
+/* Text ids (data/dataset.py:83-173, `text2id` at :175-185; collate at :187-258): item i is len[i] int32 ids at arena + off[i];
+ * out (B, 1, width) int64, out[b][0][t] = t < len[r] ? arena[off[r] + t] : 0 ('P' = id 0 is the collate's padding). */
+int ssv_corpus_gather_ids(const int* arena, long arena_n, const long* off, const int* len, int n_items, const int* rows, long n_rows,
+                          long row0, long* out, int B, int width, ssv_stream_t stream);
+
 /* ---- Second order, for the critics' gradient penalty ------------------------------------------
  * train/adversarial_wasserstein_gp.py:300-308 differentiates the critic's input gradient
  * (`autograd.grad(..., create_graph=True)` then `loss.backward()`), so the LayerNorm / highway-gate BACKWARD kernels need

@@ -121,7 +121,13 @@ class CorpusSource:
     ``extract_features_batched`` (ragged batches, resampling included).  "device" reads and writes no spectrogram cache: an item
     is its waveform, a batch's waveforms are padded and uploaded once and ``corpus_features.CorpusFeatureExtractor`` turns them into
     ``data_0`` / ``data_1`` / ``data_3`` ON THE DEVICE, in the layout and zero padding of the collated cached items (texts and speaker
-    codes stay host tensors, as today); ``last_rt`` then holds the batch's reduced frame counts, copied to the host once per batch."""
+    codes stay host tensors, as today); ``last_rt`` then holds the batch's reduced frame counts, copied to the host once per batch.
+
+    Optional config key CORPUS_RESIDENT (bool; with CORPUS_FEATURES absent, "cache" or "batched"): after the missing cache entries are filled
+    the whole cache is read ONCE into device arenas (``resident_corpus.ResidentTtsCorpus``; ``resident``), and every batch is gathered there --
+    same keys, shapes, dtypes and bits as the collated batch, already on the device.  The epoch order is the one below; its per-rank table is
+    uploaded once per epoch.  ``host_batches`` then yields bookkeeping only and ``finish_batch`` issues the gathers.  Every rank holds the whole
+    corpus.  Needs a ROCm device (``RuntimeError`` otherwise: no fallback); with "device" a ``ValueError``."""
 
     def __init__(self, cfg, step, pattern, mode, batch_size, spec_dir=None, seed=0, rank=0, world=1, stage=None):
         self.cfg, self.step, self.mode, self.B = cfg, step, mode, batch_size
@@ -141,7 +147,13 @@ class CorpusSource:
         self.features = cfg.get("CORPUS_FEATURES", "cache")
         if self.features not in ("cache", "batched", "device"):
             raise ValueError("CORPUS_FEATURES must be 'cache', 'batched' or 'device', got %r" % (self.features,))
-        self.extractor, self.last_rt = None, None
+        self.extractor, self.last_rt, self.resident = None, None, None
+        want_resident = bool(cfg.get("CORPUS_RESIDENT", False))
+        if want_resident and self.features == "device":
+            raise ValueError("CORPUS_RESIDENT with CORPUS_FEATURES='device' is not supported: 'device' keeps no spectrograms to hold; "
+                             "use 'cache' or 'batched'")
+        if want_resident and not torch.cuda.is_available():
+            raise RuntimeError("CORPUS_RESIDENT needs a ROCm device: the corpus is gathered by HIP kernels, there is no host fallback")
         if self.features == "device":
             from .corpus_features import CorpusFeatureExtractor
             self.extractor = CorpusFeatureExtractor(cfg, "cuda")              # raises without a ROCm device: no fallback
@@ -151,6 +163,10 @@ class CorpusSource:
             extract_features_batched(missing, cfg, self.cache)
         elif missing:
             extract_features(missing, cfg, self.cache)
+        if want_resident:
+            from . import resident_corpus
+            self.resident = resident_corpus.ResidentTtsCorpus(
+                resident_corpus.plan(cfg, self.wavlist, self.txtlist, self.cache, step, mode), _device())
 
     def __len__(self):
         per = self.B * self.world
@@ -210,7 +226,11 @@ class CorpusSource:
     def finish_batch(self, hb):
         """CORPUS_FEATURES = "device": a host batch of ``host_batches`` -> the training batch.  One upload of the padded waveforms, the
         extractor, one copy of the B frame counts back (``last_rt``).  Batch preparation: call it on the thread that issues the training
-        step (``Prefetcher`` does), outside any captured graph."""
+        step (``Prefetcher`` does), outside any captured graph.
+        CORPUS_RESIDENT: the bookkeeping of ``host_batches`` -> the batch, gathered from the arenas (the epoch's table is uploaded with its
+        first batch, here)."""
+        if self.resident is not None:
+            return self.resident.batch(hb["_row0"], hb["_B"], hb["_rows"])
         dev = self.extractor.device
         mel, lin, self.last_rt = self.extractor.collated(hb["_wav"].to(dev, non_blocking=True), hb["_len"].to(dev, non_blocking=True), hb["_sr"])
         out = {"data_0": mel}
@@ -224,7 +244,21 @@ class CorpusSource:
 
     def host_batches(self):
         """The batches of ``__iter__`` before any device work (what a prefetching thread may run ahead): the finished batch in the cache
-        modes, the padded waveforms with texts and speaker codes in "device" mode."""
+        modes, the padded waveforms with texts and speaker codes in "device" mode; with CORPUS_RESIDENT where the batch starts in the epoch's
+        table and how many items it has."""
+        batches = self._epoch_batches()
+        if self.resident is not None:
+            from .resident_corpus import EpochRows, epoch_rows
+            table, spans = epoch_rows(list(batches))            # this rank's whole epoch, wraps included: one upload
+            rows = EpochRows(table)
+            for row0, B in spans:
+                yield {"_rows": rows, "_row0": row0, "_B": B}
+            return
+        for idx in batches:
+            yield self._collate([self._item(int(k)) for k in idx])
+
+    def _epoch_batches(self):
+        """The item indices of this rank's batches of the next epoch, batch after batch (and the epoch counter moves on)."""
         n = len(self.wavlist)
         order = np.arange(n)
         if self.mode == "train":                                    # DataLoader(shuffle=True): a fresh permutation per epoch
@@ -239,11 +273,11 @@ class CorpusSource:
                 idx = order[np.arange(i * per + self.rank * self.B, i * per + (self.rank + 1) * self.B) % n]
             else:
                 idx = order[i * per:(i + 1) * per]                     # one process: the reference's partial last batch (drop_last=False)
-            yield self._collate([self._item(int(k)) for k in idx])
+            yield idx
 
     def __iter__(self):
         for hb in self.host_batches():
-            yield self.finish_batch(hb) if self.features == "device" else hb
+            yield self.finish_batch(hb) if (self.features == "device" or self.resident is not None) else hb
 
 
 class BatchSource:
@@ -301,8 +335,8 @@ class BatchSource:
 
     @property
     def device_features(self):
-        """True when batches are finished on the device by ``finish_batch`` (a corpus with CORPUS_FEATURES = "device")."""
-        return self.corpus is not None and self.corpus.features == "device"
+        """True when batches are finished on the device by ``finish_batch`` (a corpus with CORPUS_FEATURES = "device" or CORPUS_RESIDENT)."""
+        return self.corpus is not None and (self.corpus.features == "device" or self.corpus.resident is not None)
 
     def host_batches(self):
         return self.corpus.host_batches()
@@ -325,7 +359,8 @@ class Prefetcher:
     already on ``device``, in the same order.  Tensors that are on a device already pass through unchanged.  A source whose
     ``device_features`` is true (CORPUS_FEATURES = "device") is read through ``host_batches`` on the background thread -- file
     decoding and padding -- and each batch is finished by ``finish_batch`` HERE, on the consuming thread: the extractor issues library
-    calls and switches the library's arithmetic mode around its transforms, which must not interleave with the training step's calls."""
+    calls and switches the library's arithmetic mode around its transforms, which must not interleave with the training step's calls.
+    So is a source with CORPUS_RESIDENT: the background thread then only counts rows, and the gather kernels are issued here."""
 
     def __init__(self, source, device, depth=2):
         self.source, self.device, self.depth = source, device, depth
