@@ -711,6 +711,38 @@ size_t ssv_grad_penalty_workspace(int B, long n);
 int ssv_grad_penalty_fwd(const float* g, float* loss, float* coef, int B, long n, float lam, void* ws, size_t ws_bytes, ssv_stream_t stream);
 int ssv_grad_penalty_bwd(const float* g, const float* coef, const float* gout, float* dg, int B, long n, ssv_stream_t stream);
 
+/* ---- Spoof countermeasure: classifier head and its optimizer (additions; ABI version unchanged) -------------------------------
+ * ssv_cm_head_fwd replaces `x = self.conv5(F.leaky_relu(x, 0.05)); x = self.pl3(x); x = F.sigmoid(x)`,
+ * anti_spoofing/discriminator.py:129-131 (:91-93 for melDisc), and the loss of anti_spoofing/main_spoof_conv1d.py:87,
+ * the mean over the batch of `-label*log(pred+1e-6)-(1-label)*log(1-pred+1e-6)`, for x (B, C, T) dense, the output of ln4, C <= 16:
+ *   z_b = bias[0] + sum_c w[c] * mean_t leaky_relu(x[b,c,t], slope)   (the mean and the one-channel 1x1 convolution commute);
+ *   pred[b] = p_b = sigmoid(z_b);  per[b] = -y_b log(p_b + 1e-6) - (1 - y_b) log(q_b + 1e-6);  loss[0] = mean_b per[b].
+ * q_b = 1 - p_b is evaluated as sigmoid(-z_b): the subtraction the reference writes loses every digit of q in float32 once z
+ * exceeds about 17 and puts a wrong-label item's term off by up to 0.06 just below that; here both tails keep their relative accuracy.  The
+ * row sums are fp32 (a wave per (b, c) row); z, the sigmoids and the logarithms of an item are evaluated in double and rounded once.
+ * labels (B floats) NULL = scoring: only pred is written (amean may be given, per and loss are not touched).  With labels, amean
+ * (B, C), the activated means, is saved for the backward.  Two launches (one workgroup per item; one wave that adds the B terms
+ * in a fixed order), no atomics: bitwise reproducible.
+ * ssv_cm_head_bwd is autograd's backward of the above (`loss.backward()`, main_spoof_conv1d.py:89) down to ln4's output, gscale
+ * (DEVICE float) the gradient arriving at the loss:
+ *   dz[b] = gscale / B * p_b q_b (-y_b / (p_b + 1e-6) + (1 - y_b) / (q_b + 1e-6))   (B floats, scratch the caller provides);
+ *   dx[b,c,t] = dz[b] / T * w[c] * (x[b,c,t] > 0 ? 1 : slope);  dw[c] = sum_b dz[b] amean[b,c];  dbias[0] = sum_b dz[b].
+ * Codes: B, C, T <= 0, C > 16 or a NULL pointer: -1, before any launch. */
+int ssv_cm_head_fwd(const float* x, const float* w, const float* bias, const float* labels, float slope, float* pred, float* amean,
+                    float* per, float* loss, int B, int C, int T, ssv_stream_t stream);
+int ssv_cm_head_bwd(const float* x, const float* w, const float* bias, const float* labels, const float* amean, const float* gscale,
+                    float slope, float* dx, float* dw, float* dbias, float* dz, int B, int C, int T, ssv_stream_t stream);
+/* Replaces `optim.Adam(..., betas=(0.9, 0.98), eps=1e-09, weight_decay=1e-4, amsgrad=True)` and its .step(),
+ * anti_spoofing/main_spoof_conv1d.py:52,90, for many tensors in one launch: ssv_adam_multi with L2 weight decay and AMSGrad, in the
+ * arithmetic of torch's single-tensor path:  g' = g + wd p;  m = b1 m + (1-b1) g';  v = b2 v + (1-b2) g'^2;  vmax = max(vmax, v);
+ * p -= lr / (1 - b1^t) * m / (sqrt(vmax) / sqrt(1 - b2^t) + eps).  amsgrad == 0: v in place of vmax, and the vmax of a chunk is
+ * neither read nor written (NULL allowed).  g is only read.  chunks / step / step_dev: as ssv_adam_multi.
+ * Codes: nchunks <= 0, no step, weight_decay < 0, amsgrad not 0 / 1: -1.  The table lives on the device, so a NULL vmax under
+ * amsgrad = 1 is the caller's to refuse (FusedAdamEx checks its rows on the host). */
+typedef struct { float* p; const float* g; float* m; float* v; float* vmax; long n; } ssv_adam_ex_chunk;
+int ssv_adam_ex_multi(const ssv_adam_ex_chunk* chunks, int nchunks, float lr, float beta1, float beta2, float eps, float weight_decay,
+                      int amsgrad, int step, int* step_dev, ssv_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

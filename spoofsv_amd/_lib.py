@@ -21,6 +21,12 @@ class AdamChunk(ctypes.Structure):
                 ("v", ctypes.c_void_p), ("n", ctypes.c_long)]
 
 
+class AdamExChunk(ctypes.Structure):
+    """Mirror of ``ssv_adam_ex_chunk``."""
+    _fields_ = [("p", ctypes.c_void_p), ("g", ctypes.c_void_p), ("m", ctypes.c_void_p), ("v", ctypes.c_void_p),
+                ("vmax", ctypes.c_void_p), ("n", ctypes.c_long)]
+
+
 class ClipSgdChunk(ctypes.Structure):
     """Mirror of ``ssv_clip_sgd_chunk``."""
     _fields_ = [("p", ctypes.c_void_p), ("g", ctypes.c_void_p), ("n", ctypes.c_long), ("group", ctypes.c_int), ("pad_", ctypes.c_int)]

@@ -97,15 +97,19 @@ class _Disc(nn.Module):
         self.conv5 = nn.Conv1d(last, 1, 1)
         self.pl3 = nn.AdaptiveAvgPool1d(output_size=1)
 
-    def forward(self, inputs):
+    def trunk(self, inputs):
+        """Everything up to and including ln4 (what the countermeasure's fused head, ``ops.cm_head``, takes)."""
         tr = self.training
         x = _act(_ln(_conv(self.conv1, inputs), self.ln1), tr)
         x = self.hc(x)
         x = _ln(ops.avg_pool1d(_conv(self.conv2, x), self.pl1.kernel_size[0]), self.ln2)
         x = _act(x, tr, slope=0.05)                                       # dp2(leaky_relu(.)), one kernel
         x = _ln(ops.avg_pool1d(_conv(self.conv3, x), self.pl2.kernel_size[0]), self.ln3)
-        x = _ln(_conv(self.conv4, _act(x, tr, slope=0.05, drop=False)), self.ln4)
-        x = _conv(self.conv5, _act(x, tr, slope=0.05, drop=False))
+        return _ln(_conv(self.conv4, _act(x, tr, slope=0.05, drop=False)), self.ln4)
+
+    def forward(self, inputs):
+        x = self.trunk(inputs)
+        x = _conv(self.conv5, _act(x, self.training, slope=0.05, drop=False))
         return ops.avg_pool1d(x, x.shape[-1])                              # AdaptiveAvgPool1d(1); no sigmoid: Wasserstein critic
 
 

@@ -816,6 +816,66 @@ def grad_penalty(g, lam):
     return GradPenaltyFn.apply(g, lam)[0]
 
 
+# ------------------------------------------------------------------------------------------- countermeasure head
+class CmHeadFn(torch.autograd.Function):
+    """anti_spoofing/discriminator.py:129-131 (`conv5(leaky_relu(x, 0.05))`, `pl3`, `sigmoid`) and, with labels, the loss of
+    anti_spoofing/main_spoof_conv1d.py:87, as ``ssv_cm_head_fwd`` / ``ssv_cm_head_bwd`` (two launches each).  First order only, and only
+    through the loss: ``pred`` is returned for reporting and scoring and carries no gradient."""
+
+    @staticmethod
+    def forward(ctx, x, w, bias, labels, slope):
+        x = _c(_dev(x, "countermeasure head input"))
+        if x.dim() != 3 or w.numel() != x.shape[1] or bias.numel() != 1:
+            raise RuntimeError("cm_head: x must be (B, C, T) with a (1, C, 1) weight and a 1-element bias, got %s, %s, %s"
+                               % (tuple(x.shape), tuple(w.shape), tuple(bias.shape)))
+        B, C, T = x.shape
+        wc, bc = _c(w), _c(bias)
+        pred = torch.empty((B,), dtype=_F32, device=x.device)
+        if labels is None:
+            _lib.call("ssv_cm_head_fwd", _p(x), _p(wc), _p(bc), None, float(slope), _p(pred), None, None, None, B, C, T, _stream())
+            ctx.mark_non_differentiable(pred)
+            return pred
+        labels = _c(_dev(labels, "labels")).reshape(-1)
+        if labels.numel() != B:
+            raise RuntimeError("cm_head: %d labels for a batch of %d" % (labels.numel(), B))
+        amean = torch.empty((B, C), dtype=_F32, device=x.device)
+        per = torch.empty((B,), dtype=_F32, device=x.device)
+        loss = torch.empty((1,), dtype=_F32, device=x.device)
+        _lib.call("ssv_cm_head_fwd", _p(x), _p(wc), _p(bc), _p(labels), float(slope), _p(pred), _p(amean), _p(per), _p(loss), B, C, T, _stream())
+        ctx.save_for_backward(x, wc, bc, labels, amean)
+        ctx.slope, ctx.wshape, ctx.bshape = float(slope), w.shape, bias.shape
+        ctx.mark_non_differentiable(pred)
+        return loss.view(()), pred
+
+    @staticmethod
+    def backward(ctx, gloss, gpred=None):
+        if torch.is_grad_enabled():          # create_graph=True: once_differentiable alone would hand back gradients without a graph
+            raise RuntimeError("spoofsv_amd: ops.cm_head is differentiable once -- its backward kernel (ssv_cm_head_bwd) has no gradient of "
+                               "its own, so create_graph=True / a gradient penalty through the countermeasure head is not supported")
+        return CmHeadFn._backward_once(ctx, gloss)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def _backward_once(ctx, gloss):
+        x, w, bias, labels, amean = ctx.saved_tensors
+        B, C, T = x.shape
+        dx = torch.empty_like(x)
+        dw = torch.empty((C,), dtype=_F32, device=x.device)
+        db = torch.empty((1,), dtype=_F32, device=x.device)
+        dz = torch.empty((B,), dtype=_F32, device=x.device)
+        _lib.call("ssv_cm_head_bwd", _p(x), _p(w), _p(bias), _p(labels), _p(amean), _p(_c(gloss)), ctx.slope, _p(dx), _p(dw), _p(db), _p(dz),
+                  B, C, T, _stream())
+        return dx, dw.view(ctx.wshape), db.view(ctx.bshape), None, None
+
+
+def cm_head(x, w, bias, labels=None, slope=0.05):
+    """The countermeasure's classifier head on ``x`` (B, C <= 16, T), the output of ln4: ``pred`` (B,) = sigmoid(bias + sum_c w[c]
+    mean_t leaky_relu(x, slope)) without labels; with ``labels`` (B,) in {0, 1} (float) ``(loss, pred)``, loss the mean binary
+    cross-entropy with the reference's 1e-6 inside the logarithms.  Differentiable once, through ``loss`` (a second-order use raises:
+    the backward is marked ``once_differentiable``); ``pred`` carries no gradient."""
+    return CmHeadFn.apply(x, w, bias, labels, slope)
+
+
 # ------------------------------------------------------------------------------------------- critics: LayerNorm / gate, twice differentiable
 # models/discriminator.py:24-41 (LayerNorm over channels between the critic's convs) and models/TTSModel_dropout.py:63-84
 # (the highway gate), for the WGAN-GP critics.  The gradient penalty (train/adversarial_wasserstein_gp.py:300-308) takes the

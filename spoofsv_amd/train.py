@@ -102,35 +102,53 @@ class FusedAdam(torch.optim.Optimizer):
             self._resident = _resident.ResidentWeights([p for g in self.param_groups for p in g["params"]])
         self._resident.refresh(_stream())
 
+    # What a subclass with more state per parameter changes (FusedAdamEx): the chunk struct, its moment tensors, the launch.
+    _CHUNK_STRUCT = _lib.AdamChunk
+    _COLS = 5
+
+    def _moments(self, p):
+        """The moment tensors of ``p`` in the order of the chunk struct's fields behind p and g, created on first use (None: a null field)."""
+        st = self.state[p]
+        if "exp_avg" not in st:
+            st["step"] = torch.tensor(0.0)
+            st["exp_avg"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
+            st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
+        return st["exp_avg"], st["exp_avg_sq"]
+
+    def _check_rows(self, rows):
+        pass
+
+    def _launch(self, group, step_dev):
+        b1, b2 = group["betas"]
+        _lib.call("ssv_adam_multi", _p(self._table), self._nchunks, float(group["lr"]), float(b1), float(b2),
+                  float(group["eps"]), self._steps, step_dev, _stream())
+
     def _build(self, plist):
         key = tuple((p.data_ptr(), p.grad.data_ptr()) for p in plist)
         if key == self._key:
             return
         rows = []
         for p in plist:
-            st = self.state[p]
-            if "exp_avg" not in st:
-                st["step"] = torch.tensor(0.0)
-                st["exp_avg"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
-                st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
+            moments = self._moments(p)
             if not (p.is_contiguous() and p.grad.is_contiguous() and p.dtype == torch.float32 and p.grad.dtype == torch.float32):
                 raise RuntimeError("FusedAdam needs dense float32 parameters and gradients")
             n = p.numel()
             for off in range(0, n, _CHUNK):
                 m = min(_CHUNK, n - off)
-                rows.append((p.data_ptr() + 4 * off, p.grad.data_ptr() + 4 * off, st["exp_avg"].data_ptr() + 4 * off,
-                             st["exp_avg_sq"].data_ptr() + 4 * off, m))
+                rows.append((p.data_ptr() + 4 * off, p.grad.data_ptr() + 4 * off) + tuple(0 if t is None else t.data_ptr() + 4 * off for t in moments) + (m,))
+        self._check_rows(rows)
         arr = np.array(rows, dtype=np.int64)
-        assert ctypes.sizeof(_lib.AdamChunk) == 40
+        cols = self._COLS
+        assert ctypes.sizeof(self._CHUNK_STRUCT) == 8 * cols and arr.shape[1] == cols
         # Pinned staging buffer + async copy, both allocated once (sized for every parameter): refilling
         # them is legal while a hipGraph is being captured (the copy becomes a memcpy node).
         # Two pinned tables used alternately, and an event after each copy: a rebuild (gradient addresses can move between
         # eager iterations) must not overwrite a pinned table whose asynchronous copy has not executed yet.
         if self._host_tables is None:
             cap = sum((p.numel() + _CHUNK - 1) // _CHUNK for g in self.param_groups for p in g["params"])
-            self._host_tables = [torch.empty((cap, 5), dtype=torch.int64).pin_memory() for _ in range(2)]
+            self._host_tables = [torch.empty((cap, cols), dtype=torch.int64).pin_memory() for _ in range(2)]
             self._copied = [None, None]
-            self._table = torch.empty((cap, 5), dtype=torch.int64, device=plist[0].device)
+            self._table = torch.empty((cap, cols), dtype=torch.int64, device=plist[0].device)
         self._host_flip ^= 1
         host, ev = self._host_tables[self._host_flip], self._copied[self._host_flip]
         capturing = torch.cuda.is_current_stream_capturing()
@@ -157,14 +175,12 @@ class FusedAdam(torch.optim.Optimizer):
             ops._dev(plist[0], "parameter")
             self._build(plist)
             self._steps += 1
-            b1, b2 = group["betas"]
             step_dev = None
             if self.capturable:
                 if self._step_dev is None:
                     self._step_dev = torch.full((1,), self._steps - 1, dtype=torch.int32, device=plist[0].device)
                 step_dev = _p(self._step_dev)
-            _lib.call("ssv_adam_multi", _p(self._table), self._nchunks, float(group["lr"]), float(b1), float(b2),
-                      float(group["eps"]), self._steps, step_dev, _stream())
+            self._launch(group, step_dev)
         self.refresh_resident_weights()
         return loss
 
@@ -186,6 +202,55 @@ class FusedAdam(torch.optim.Optimizer):
         if self._step_dev is not None:
             self._step_dev.fill_(self._steps)
         self._key = None                      # moment tensors were replaced: rebuild the chunk table
+
+
+def check_adam_ex_rows(rows, amsgrad):
+    """Host-side check of an ``ssv_adam_ex_chunk`` table before it is uploaded (the kernel cannot refuse a table it reads on the device):
+    every row (p, g, m, v, vmax, n) has non-null p, g, m, v and n > 0, and a non-null vmax when ``amsgrad``."""
+    for i, r in enumerate(rows):
+        if len(r) != 6:
+            raise ValueError("adam_ex chunk %d has %d fields, expected (p, g, m, v, vmax, n)" % (i, len(r)))
+        if not (r[0] and r[1] and r[2] and r[3]) or int(r[5]) <= 0:
+            raise ValueError("adam_ex chunk %d: null p, g, m or v, or n = %d" % (i, int(r[5])))
+        if amsgrad and not r[4]:
+            raise ValueError("adam_ex chunk %d: amsgrad needs max_exp_avg_sq, got a null vmax" % i)
+
+
+class FusedAdamEx(FusedAdam):
+    """``torch.optim.Adam(params, lr, betas, eps, weight_decay, amsgrad)`` as the countermeasure's trainer uses it
+    (anti_spoofing/main_spoof_conv1d.py:52: betas (0.9, 0.98), eps 1e-9, weight_decay 1e-4, amsgrad) on ONE multi-tensor launch
+    (``ssv_adam_ex_multi``): L2 weight decay folded into the gradient, AMSGrad's running maximum of the second moment.  State keys
+    (``step``, ``exp_avg``, ``exp_avg_sq``, ``max_exp_avg_sq`` under amsgrad) and param-group keys are torch's, so a state dict loads into
+    ``torch.optim.Adam(amsgrad=True)`` and back (the reference's ``-R`` resume).  Chunk table, pinned staging, device step counter, step
+    export and the refresh of resident conv planes are ``FusedAdam``'s."""
+
+    _CHUNK_STRUCT = _lib.AdamExChunk
+    _COLS = 6
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, amsgrad=False, capturable=False, resident=True):
+        if weight_decay < 0:
+            raise ValueError("Invalid weight_decay value: %r" % (weight_decay,))
+        super().__init__(params, lr, betas, eps, capturable=capturable, resident=resident)
+        self.defaults.update(weight_decay=weight_decay, amsgrad=bool(amsgrad))
+        for g in self.param_groups:
+            g.update(weight_decay=weight_decay, amsgrad=bool(amsgrad))
+
+    def _moments(self, p):
+        m, v = super()._moments(p)
+        st = self.state[p]
+        if not self.param_groups[0]["amsgrad"]:
+            return m, v, None
+        if "max_exp_avg_sq" not in st:
+            st["max_exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
+        return m, v, st["max_exp_avg_sq"]
+
+    def _check_rows(self, rows):
+        check_adam_ex_rows(rows, self.param_groups[0]["amsgrad"])
+
+    def _launch(self, group, step_dev):
+        b1, b2 = group["betas"]
+        _lib.call("ssv_adam_ex_multi", _p(self._table), self._nchunks, float(group["lr"]), float(b1), float(b2), float(group["eps"]),
+                  float(group["weight_decay"]), int(bool(group["amsgrad"])), self._steps, step_dev, _stream())
 
 
 class TrainingSnapshot:
