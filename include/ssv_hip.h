@@ -647,12 +647,15 @@ int ssv_highway_gate_bwd2(const float* vh, const float* vx, long vx_bs, const fl
  * ssv_column_matvec: out[b][m] = bias[m] + bias_b[b][m] + sum_{j,c} w[m][j][c] x_j[b][c] with w TAP-MAJOR, (M, k, C) =
  * nn.Conv1d's (M, C, k) weight with its last two axes swapped (the weights are frozen during synthesis: permute once; for
  * k = 1 the layouts coincide).  C a multiple of 4, buffers 16-byte aligned.  k = 1: x_0 = cur.  k = 3 (causal, `dilation`): x_2 = cur (frame t = *t_dev), x_1 = hist[t-d], x_0 = hist[t-2d]
- * (zero before frame 0); cur is also stored as column t of hist.  bias, bias_b, and (k = 1) hist / t_dev may be NULL. */
+ * (a tap outside [0, Tmax) is zero); cur is also stored as column t of hist when 0 <= t < Tmax.  A frame counter outside the history
+ * (a replay past the last frame, as ssv_attention_column and ssv_synth_column_advance tolerate) reads and writes nothing outside hist;
+ * out is still written.  bias, bias_b, and (k = 1) hist / t_dev may be NULL.  cur_bs and hist_bs are multiples of 4 floats. */
 int ssv_column_matvec(const float* w, const float* bias, const float* bias_b, long bb_bs, const float* cur, long cur_bs,
                       float* hist, long hist_bs, int Tmax, const int* t_dev, int dilation, float* out, long out_bs,
                       int B, int C, int M, int k, ssv_stream_t stream);
 /* LayerNorm over channels (+ activation, as ssv_channel_ln_act_fwd) and the highway gate (as ssv_highway_gate_fwd, h (B,2C)
- * dense) on one column per batch item. */
+ * dense) on one column per batch item, C <= 1024.  The mean is the correctly rounded sum / C: a column of one constant whose
+ * sum is exact in float32 gives act(beta) to the bit. */
 int ssv_column_ln_act(const float* x, long x_bs, const float* gamma, const float* beta, float* y, long y_bs, int B, int C, int act,
                       ssv_stream_t stream);
 int ssv_column_gate(const float* h, const float* x, long x_bs, const float* g1, const float* b1, const float* g2, const float* b2,

@@ -11,8 +11,10 @@
 #define CMV_KMAX 1536     // C * k
 
 // out[b][m] = bias[m] + bias_b[b][m] + sum_{j, c} w[m][j][c] * x_j[b][c]        (w TAP-MAJOR: (M, k, C), see ssv_hip.h)
-//   k = 1: x_0 = cur.   k = 3 (causal, dilation d): x_2 = cur (column t), x_1 = hist[t - d], x_0 = hist[t - 2d], zero before 0.
-// By-product (row block 0): cur is stored as column t of hist, for the steps to come.
+//   k = 1: x_0 = cur.   k = 3 (causal, dilation d): x_2 = cur (column t), x_1 = hist[t - d], x_0 = hist[t - 2d]; a tap outside
+//   [0, Tmax) is zero (as in the wide step, synth_wide.hip).
+// By-product (row block 0): cur is stored as column t of hist, for the steps to come, when 0 <= t < Tmax.  A frame counter outside
+// the history (a replay past the last frame) therefore reads and writes nothing outside it.
 // Workgroup (x, y): output rows 4x..4x+3 (one per wave) for batch items 8y..8y+7.  The staged inputs are the k columns
 // one after the other, like a tap-major weight row, so a row is one contiguous dot product of length K = k*C.  In a wave, lane = 8*bb + ks:
 // the 8 lanes of a batch item take every 8th float4 of the row (a weight read is 128 contiguous bytes, shared by the 8
@@ -50,10 +52,10 @@ __global__ __launch_bounds__(256) void column_matvec_kernel(
       if (bi < B) {
         if (j == KT - 1) {
           v = *reinterpret_cast<const f32x4*>(cur + (long)bi * cur_bs + c);
-          if (KT > 1 && blockIdx.x == 0 && t < Tmax) *reinterpret_cast<f32x4*>(hist + (long)bi * hist_bs + (long)t * C + c) = v;
+          if (KT > 1 && blockIdx.x == 0 && t >= 0 && t < Tmax) *reinterpret_cast<f32x4*>(hist + (long)bi * hist_bs + (long)t * C + c) = v;
         } else {
           const int col = t - (KT - 1 - j) * dil;
-          if (col >= 0) v = *reinterpret_cast<const f32x4*>(hist + (long)bi * hist_bs + (long)col * C + c);
+          if (col >= 0 && col < Tmax) v = *reinterpret_cast<const f32x4*>(hist + (long)bi * hist_bs + (long)col * C + c);
         }
       }
       *reinterpret_cast<f32x4*>(xs + bb * KP + 4 * i) = v;
@@ -117,6 +119,13 @@ __device__ __forceinline__ float block_sum(float v, float* red) {        // sum 
   return (red[0] + red[1]) + (red[2] + red[3]);
 }
 #define COL_CPT 4         // channels per thread: C <= 1024
+// sum / n correctly rounded, for inv = 1.f / n computed ahead of the reduction: the division's own last step (the residual sum - n q is exact
+// in one fma) instead of its whole sequence behind the reduction.  Plain sum * inv would be contracted into v - mu as fma(-inv, sum, v) and
+// keep the 2^-24 of the rounded reciprocal: a column of one constant c then comes out as beta + gamma * c * 2e-5 (rsqrt(eps) = 316), not beta.
+__device__ __forceinline__ float col_mean(float sum, float n, float inv) {
+  const float q = __fmul_rn(sum, inv);
+  return fmaf(fmaf(-q, n, sum), inv, q);
+}
 __global__ __launch_bounds__(256) void column_ln_act_kernel(const float* __restrict__ x, long x_bs, const float* __restrict__ gam,
                                                             const float* __restrict__ bet, float* __restrict__ y, long y_bs, int C, int act) {
   __shared__ float red[4];
@@ -124,7 +133,7 @@ __global__ __launch_bounds__(256) void column_ln_act_kernel(const float* __restr
   float v[COL_CPT], s = 0.f;
 #pragma unroll
   for (int i = 0; i < COL_CPT; ++i) { const int c = threadIdx.x + 256 * i; v[i] = c < C ? xb[c] : 0.f; s += v[i]; }
-  const float inv = 1.f / (float)C, mu = block_sum(s, red) * inv;
+  const float fC = (float)C, inv = 1.f / fC, mu = col_mean(block_sum(s, red), fC, inv);
   float q = 0.f;
 #pragma unroll
   for (int i = 0; i < COL_CPT; ++i) { const float dlt = (threadIdx.x + 256 * i) < C ? v[i] - mu : 0.f; q += dlt * dlt; }
@@ -154,8 +163,8 @@ __global__ __launch_bounds__(256) void column_gate_kernel(const float* __restric
     u[i] = c < C ? h1[c] : 0.f; v[i] = c < C ? h2[c] : 0.f;
     s1 += u[i]; s2 += v[i];
   }
-  const float inv = 1.f / (float)C;
-  const float mu1 = block_sum(s1, red) * inv, mu2 = block_sum(s2, red) * inv;
+  const float fC = (float)C, inv = 1.f / fC;
+  const float mu1 = col_mean(block_sum(s1, red), fC, inv), mu2 = col_mean(block_sum(s2, red), fC, inv);
   float q1 = 0.f, q2 = 0.f;
 #pragma unroll
   for (int i = 0; i < COL_CPT; ++i) {
