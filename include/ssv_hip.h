@@ -616,6 +616,17 @@ int ssv_corpus_gather(const float* arena, long arena_n, const long* off, const i
 int ssv_corpus_gather_ids(const int* arena, long arena_n, const long* off, const int* len, int n_items, const int* rows, long n_rows,
                           long row0, long* out, int B, int width, ssv_stream_t stream);
 
+/* The inverse of ssv_corpus_gather, for filling an arena on the device: replaces the per-item `lin_spec`, `mel_spec = self.get_spec(...)`
+ * of ASVspoofDataset.__getitem__, anti_spoofing/spoof_conv1d.py:43-91, run again for every item of every epoch, by ONE extraction whose
+ * collated batches (collate_pad_3, main_spoof_conv1d.py:64) are filed item by item.  src (B, F, width), batch stride src_bs elements, is
+ * a collated batch; item i = item0 + b of the arena (off, len: n_items entries on the DEVICE, as above) receives
+ * arena[off[i] + f * len[i] + t] = src[b * src_bs + f * width + t] for f < F, t < len[i].  Nothing is read on the host.  An item with
+ * len[i] < 0 or len[i] > width, or whose block does not lie inside the arena_n elements of the arena, is left untouched and nothing else
+ * changes.  16-byte accesses where a row starts on a 16-byte boundary on both sides, 4-byte ones elsewhere.
+ * Codes: NULL pointers, non-positive sizes, [item0, item0 + B) outside the table, src_bs < F * width: -1; a grid that does not fit: -2. */
+int ssv_corpus_scatter(const float* src, long src_bs, int B, int F, int width, float* arena, long arena_n, const long* off, const int* len,
+                       int n_items, int item0, ssv_stream_t stream);
+
 /* ---- Second order, for the critics' gradient penalty ------------------------------------------
  * train/adversarial_wasserstein_gp.py:300-308 differentiates the critic's input gradient
  * (`autograd.grad(..., create_graph=True)` then `loss.backward()`), so the LayerNorm / highway-gate BACKWARD kernels need
@@ -735,6 +746,17 @@ int ssv_cm_head_fwd(const float* x, const float* w, const float* bias, const flo
                     float* per, float* loss, int B, int C, int T, ssv_stream_t stream);
 int ssv_cm_head_bwd(const float* x, const float* w, const float* bias, const float* labels, const float* amean, const float* gscale,
                     float slope, float* dx, float* dw, float* dbias, float* dz, int B, int C, int T, ssv_stream_t stream);
+/* ssv_cm_head_fwd / ssv_cm_head_bwd (anti_spoofing/discriminator.py:129-131, main_spoof_conv1d.py:87,89) on an x (B, C, T) of which only
+ * the first Tl = clamp(live[0], 1, T) columns are live: a batch gathered into a wider static buffer, so that the iteration of
+ * main_spoof_conv1d.py:84-90 can be replayed from one captured hipGraph per width.  live is a DEVICE int read when the kernels run.  The
+ * means and the dz / T of the backward use Tl; columns t >= Tl of x are never used (they may hold anything, NaN included) and dx is
+ * written as exact zeros there.  Same kernels as the dense entries (the same two launches each way, no atomics, the same summation
+ * order, the double-precision scalar tail, q = sigmoid(-z)): with live[0] == T every output has the bits of ssv_cm_head_fwd / _bwd.
+ * Codes: those of the dense entries; a NULL live: -1. */
+int ssv_cm_head_fwd_len(const float* x, const float* w, const float* bias, const float* labels, float slope, float* pred, float* amean,
+                        float* per, float* loss, int B, int C, int T, const int* live, ssv_stream_t stream);
+int ssv_cm_head_bwd_len(const float* x, const float* w, const float* bias, const float* labels, const float* amean, const float* gscale,
+                        float slope, float* dx, float* dw, float* dbias, float* dz, int B, int C, int T, const int* live, ssv_stream_t stream);
 /* Replaces `optim.Adam(..., betas=(0.9, 0.98), eps=1e-09, weight_decay=1e-4, amsgrad=True)` and its .step(),
  * anti_spoofing/main_spoof_conv1d.py:52,90, for many tensors in one launch: ssv_adam_multi with L2 weight decay and AMSGrad, in the
  * arithmetic of torch's single-tensor path:  g' = g + wd p;  m = b1 m + (1-b1) g';  v = b2 v + (1-b2) g'^2;  vmax = max(vmax, v);

@@ -97,11 +97,15 @@ class _Disc(nn.Module):
         self.conv5 = nn.Conv1d(last, 1, 1)
         self.pl3 = nn.AdaptiveAvgPool1d(output_size=1)
 
-    def trunk(self, inputs):
-        """Everything up to and including ln4 (what the countermeasure's fused head, ``ops.cm_head``, takes)."""
+    def trunk(self, inputs, live=None):
+        """Everything up to and including ln4 (what the countermeasure's fused head, ``ops.cm_head``, takes).  ``live`` (an ``ops.Live``):
+        ``inputs`` is a batch padded to a wider buffer and only its first ``live`` columns are real.  ``hc``'s kernel-3 convolution is the
+        one operator that mixes columns: its input is zeroed at and past ``live`` (and the gradient on both sides of ``hc`` with it), so
+        the live columns of everything downstream are those of the unpadded batch; the 1x1 convolutions, LayerNorms and activations are
+        column-local, and every pool window that lies inside the live width reads live columns only."""
         tr = self.training
         x = _act(_ln(_conv(self.conv1, inputs), self.ln1), tr)
-        x = self.hc(x)
+        x = ops.mask_cols(self.hc(ops.mask_cols(x, live)), live)
         x = _ln(ops.avg_pool1d(_conv(self.conv2, x), self.pl1.kernel_size[0]), self.ln2)
         x = _act(x, tr, slope=0.05)                                       # dp2(leaky_relu(.)), one kernel
         x = _ln(ops.avg_pool1d(_conv(self.conv3, x), self.pl2.kernel_size[0]), self.ln3)

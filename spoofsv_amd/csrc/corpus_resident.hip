@@ -72,6 +72,30 @@ __global__ __launch_bounds__(CG_THREADS) void corpus_gather_ids_kernel(const int
   out[(long)b * width + t] = !ok ? -1L : (t < n ? (long)arena[o + t] : 0L);
 }
 
+// ---- arena[off[i] + f * len[i] + t] = src[b][f][t] for t < len[i],  i = item0 + b: the inverse of corpus_gather_kernel --------------
+// The same decomposition: workgroup (b, group of CG_ROWS rows), one wave per row, lane = t fastest; 16-byte accesses when the row starts
+// on a 16-byte boundary on both sides, the last partial quad and every other row float by float, so nothing past the item's own row is
+// written.  An item that does not fit -- len < 0, len > width (the batch does not hold all of it), a block that leaves the arena -- is
+// left alone: no word of the arena changes for it.
+__global__ __launch_bounds__(CG_THREADS) void corpus_scatter_kernel(const float* __restrict__ src, long src_bs, float* __restrict__ arena, long arena_n,
+                                                                    const long* __restrict__ off, const int* __restrict__ len, int item0, int F,
+                                                                    int width, int groups) {
+  const int b = blockIdx.x / groups, f = (blockIdx.x % groups) * CG_ROWS + (int)(threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (f >= F) return;
+  const long o = off[item0 + b];
+  const int n = len[item0 + b];
+  if (n < 0 || n > width || o < 0 || o > arena_n || (long)F * n > arena_n - o) return;
+  const float* from = src + (long)b * src_bs + (long)f * width;
+  float* dst = arena + o + (long)f * n;
+  int t0 = 0;
+  if ((((uintptr_t)from | (uintptr_t)dst) & 15) == 0) {
+    const int nq = n & ~3;
+    for (int t = lane * 4; t < nq; t += 256) *(f32x4*)(dst + t) = *(const f32x4*)(from + t);
+    t0 = nq;
+  }
+  for (int t = t0 + lane; t < n; t += 64) dst[t] = from[t];
+}
+
 extern "C" int ssv_corpus_gather(const float* arena, long arena_n, const long* off, const int* len, int n_items, const int* rows, long n_rows,
                                  long row0, float* out, int B, int F, int width, long out_bs, ssv_stream_t stream) {
   SSV_CHECK(arena && off && len && rows && out && arena_n > 0 && n_items > 0 && B > 0 && F > 0 && width > 0, SSV_BAD_SHAPE,
@@ -95,4 +119,17 @@ extern "C" int ssv_corpus_gather_ids(const int* arena, long arena_n, const long*
   hipLaunchKernelGGL(corpus_gather_ids_kernel, dim3(B * tiles), dim3(CG_THREADS), 0, (hipStream_t)stream, arena, arena_n, off, len, n_items, rows + row0, out,
                      width, tiles);
   return ssv_check_launch("corpus_gather_ids");
+}
+
+extern "C" int ssv_corpus_scatter(const float* src, long src_bs, int B, int F, int width, float* arena, long arena_n, const long* off, const int* len,
+                                  int n_items, int item0, ssv_stream_t stream) {
+  SSV_CHECK(src && arena && off && len && arena_n > 0 && n_items > 0 && B > 0 && F > 0 && width > 0, SSV_BAD_SHAPE,
+            "corpus_scatter: null pointer or empty problem (arena_n=%ld n_items=%d B=%d F=%d width=%d)", arena_n, n_items, B, F, width);
+  SSV_CHECK(item0 >= 0 && item0 <= n_items - B, SSV_BAD_SHAPE, "corpus_scatter: items [%d, %d + %d) leave the table of %d", item0, item0, B, n_items);
+  SSV_CHECK(src_bs >= (long)F * width, SSV_BAD_SHAPE, "corpus_scatter: batch stride %ld below F * width = %ld", src_bs, (long)F * width);
+  const int groups = ssv_cdiv(F, CG_ROWS);
+  SSV_CHECK((long)B * groups <= 0x7fffffffL, SSV_UNSUPPORTED, "corpus_scatter: B=%d x %d row groups exceed the grid", B, groups);
+  hipLaunchKernelGGL(corpus_scatter_kernel, dim3(B * groups), dim3(CG_THREADS), 0, (hipStream_t)stream, src, src_bs, arena, arena_n, off, len, item0, F,
+                     width, groups);
+  return ssv_check_launch("corpus_scatter");
 }

@@ -38,21 +38,31 @@ __device__ __forceinline__ double cm_bce(CmItem s, double y) { return -y * log(s
 // d per_b / d z_b = p q (-y / (p + 1e-6) + (1 - y) / (q + 1e-6))
 __device__ __forceinline__ double cm_dz(CmItem s, double y) { return s.p * s.q * (-y / (s.p + 1e-6) + (1.0 - y) / (s.q + 1e-6)); }
 
+// The live width of a padded item (the _len entries): its first clamp(live[0], 1, T) columns, live a DEVICE int read when the kernel
+// runs, so that one captured launch serves every batch of its bucket.  LEN = false is the dense head: Tl = T, nothing is read.
+template <bool LEN>
+__device__ __forceinline__ int cm_live(const int* __restrict__ live, int T) {
+  return LEN ? min(max(live[0], 1), T) : T;
+}
+
 // ---- forward, launch 1: grid = B, 256 threads.  Wave v sums the activated rows c = v, v + 4, ... of its item (lanes stride the
 // row, 16-byte loads when the row starts on a 16-byte boundary, then the wave butterfly), the means meet in LDS, and thread 0
-// finishes the item.
+// finishes the item.  Rows are T apart; the sums and the mean run over the first Tl columns, and nothing at or past Tl is loaded.
+template <bool LEN>
 __global__ __launch_bounds__(256) void cm_head_fwd_kernel(const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ bias,
                                                           const float* __restrict__ labels, float slope, float* __restrict__ pred,
-                                                          float* __restrict__ amean, float* __restrict__ per, int C, int T) {
+                                                          float* __restrict__ amean, float* __restrict__ per, int C, int T,
+                                                          const int* __restrict__ live) {
   __shared__ float am[CM_MAX_C];
   const int b = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const float inv_t = 1.f / (float)T;
+  const int Tl = cm_live<LEN>(live, T);
+  const float inv_t = 1.f / (float)Tl;
   for (int c = wave; c < C; c += 4) {
     const float* __restrict__ xr = x + ((long)b * C + c) * T;
     float s = 0.f;
     int t0 = 0;
     if ((((uintptr_t)xr) & 15) == 0) {
-      const int n4 = T >> 2;
+      const int n4 = Tl >> 2;
       const f32x4* __restrict__ x4 = reinterpret_cast<const f32x4*>(xr);
       for (int i = lane; i < n4; i += 64) {
         const f32x4 v = x4[i];
@@ -61,7 +71,7 @@ __global__ __launch_bounds__(256) void cm_head_fwd_kernel(const float* __restric
       }
       t0 = n4 << 2;
     }
-    for (int t = t0 + lane; t < T; t += 64) {
+    for (int t = t0 + lane; t < Tl; t += 64) {
       const float v = xr[t];
       s += v > 0.f ? v : slope * v;
     }
@@ -85,12 +95,14 @@ __global__ __launch_bounds__(64) void cm_loss_kernel(const float* __restrict__ p
 }
 
 // ---- backward, launch 1: grid = B, 256 threads.  dz_b once per item (recomputed from the saved means: the saved float32 pred
-// cannot give q back), then dx[b,c,t] = dz_b / T * w[c] * (x > 0 ? 1 : slope) over the item's C * T elements.
+// cannot give q back), then dx[b,c,t] = dz_b / Tl * w[c] * (x > 0 ? 1 : slope) over the item's C * T elements; with LEN the columns at or
+// past Tl are written as exact zeros whatever x holds there (a NaN compares false and is then discarded).
+template <bool LEN>
 __global__ __launch_bounds__(256) void cm_head_bwd_kernel(const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ bias,
                                                           const float* __restrict__ labels, const float* __restrict__ amean,
                                                           const float* __restrict__ gscale, float slope, float* __restrict__ dx,
-                                                          float* __restrict__ dz, int B, int C, int T) {
-  __shared__ float wz[CM_MAX_C];      // dz_b / T * w[c]
+                                                          float* __restrict__ dz, int B, int C, int T, const int* __restrict__ live) {
+  __shared__ float wz[CM_MAX_C];      // dz_b / Tl * w[c]
   __shared__ float dzs;
   const int b = blockIdx.x;
   if (threadIdx.x == 0) {
@@ -100,7 +112,8 @@ __global__ __launch_bounds__(256) void cm_head_bwd_kernel(const float* __restric
     dz[b] = d;
   }
   __syncthreads();
-  if (threadIdx.x < C) wz[threadIdx.x] = dzs / (float)T * w[threadIdx.x];
+  const unsigned uTl = (unsigned)cm_live<LEN>(live, T);
+  if (threadIdx.x < C) wz[threadIdx.x] = dzs / (float)uTl * w[threadIdx.x];
   __syncthreads();
   const unsigned n = (unsigned)C * (unsigned)T, uT = (unsigned)T;      // T <= 2^26 (checked by the entry point): an item's index fits 32 bits
   const float* __restrict__ xb = x + (long)b * n;
@@ -113,16 +126,19 @@ __global__ __launch_bounds__(256) void cm_head_bwd_kernel(const float* __restric
       f32x4 o;
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
-        const float g = wz[(4 * i + k) / uT];
+        const unsigned c = (4 * i + k) / uT;
+        const float g = wz[c];
         o[k] = v[k] > 0.f ? g : g * slope;
+        if (LEN && 4 * i + k - c * uT >= uTl) o[k] = 0.f;
       }
       reinterpret_cast<f32x4*>(db)[i] = o;
     }
     e0 = n4 << 2;
   }
   for (unsigned e = e0 + threadIdx.x; e < n; e += 256) {
-    const float g = wz[e / uT];
-    db[e] = xb[e] > 0.f ? g : g * slope;
+    const unsigned c = e / uT;
+    const float g = wz[c];
+    db[e] = (LEN && e - c * uT >= uTl) ? 0.f : (xb[e] > 0.f ? g : g * slope);
   }
 }
 // ---- backward, launch 2: one wave.  dw[c] = sum_b dz_b amean[b,c] (lane c, items in order), dbias = sum_b dz_b (lane 16).
@@ -140,31 +156,58 @@ __global__ __launch_bounds__(64) void cm_head_bwd_params_kernel(const float* __r
   }
 }
 
-extern "C" int ssv_cm_head_fwd(const float* x, const float* w, const float* bias, const float* labels, float slope, float* pred, float* amean,
-                               float* per, float* loss, int B, int C, int T, ssv_stream_t stream) {
-  SSV_CHECK(B > 0 && C > 0 && T > 0, SSV_BAD_SHAPE, "cm_head_fwd: need B, C, T > 0, got B=%d C=%d T=%d", B, C, T);
-  SSV_CHECK(C <= CM_MAX_C, SSV_BAD_SHAPE, "cm_head_fwd: C=%d exceeds the %d channels the head is built for", C, CM_MAX_C);
-  SSV_CHECK(x && w && bias && pred, SSV_BAD_SHAPE, "cm_head_fwd: null x, w, bias or pred");
-  SSV_CHECK(!labels || (amean && per && loss), SSV_BAD_SHAPE, "cm_head_fwd: with labels, amean, per and loss are outputs and must not be null");
+// One body for the dense entries (live == NULL) and the _len ones: the same kernels, instantiated with and without the live width.
+static int cm_head_fwd_run(const char* name, bool len, const float* x, const float* w, const float* bias, const float* labels, float slope,
+                           float* pred, float* amean, float* per, float* loss, int B, int C, int T, const int* live, ssv_stream_t stream) {
+  SSV_CHECK(B > 0 && C > 0 && T > 0, SSV_BAD_SHAPE, "%s: need B, C, T > 0, got B=%d C=%d T=%d", name, B, C, T);
+  SSV_CHECK(C <= CM_MAX_C, SSV_BAD_SHAPE, "%s: C=%d exceeds the %d channels the head is built for", name, C, CM_MAX_C);
+  SSV_CHECK(x && w && bias && pred, SSV_BAD_SHAPE, "%s: null x, w, bias or pred", name);
+  SSV_CHECK(!len || live, SSV_BAD_SHAPE, "%s: null live", name);
+  SSV_CHECK(!labels || (amean && per && loss), SSV_BAD_SHAPE, "%s: with labels, amean, per and loss are outputs and must not be null", name);
   hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(cm_head_fwd_kernel, dim3(B), dim3(256), 0, st, x, w, bias, labels, slope, pred, amean, per, C, T);
-  SSV_TRY(ssv_check_launch("cm_head_fwd"));
+  if (len)
+    hipLaunchKernelGGL(cm_head_fwd_kernel<true>, dim3(B), dim3(256), 0, st, x, w, bias, labels, slope, pred, amean, per, C, T, live);
+  else
+    hipLaunchKernelGGL(cm_head_fwd_kernel<false>, dim3(B), dim3(256), 0, st, x, w, bias, labels, slope, pred, amean, per, C, T, live);
+  SSV_TRY(ssv_check_launch(name));
   if (labels) {
     hipLaunchKernelGGL(cm_loss_kernel, dim3(1), dim3(64), 0, st, (const float*)per, loss, B);
     return ssv_check_launch("cm_loss");
   }
   return 0;
 }
-extern "C" int ssv_cm_head_bwd(const float* x, const float* w, const float* bias, const float* labels, const float* amean, const float* gscale,
-                               float slope, float* dx, float* dw, float* dbias, float* dz, int B, int C, int T, ssv_stream_t stream) {
-  SSV_CHECK(B > 0 && C > 0 && T > 0, SSV_BAD_SHAPE, "cm_head_bwd: need B, C, T > 0, got B=%d C=%d T=%d", B, C, T);
-  SSV_CHECK(C <= CM_MAX_C && T <= (1 << 26), SSV_BAD_SHAPE, "cm_head_bwd: C=%d exceeds the %d channels the head is built for (or T=%d exceeds 2^26)", C, CM_MAX_C, T);
-  SSV_CHECK(x && w && bias && labels && amean && gscale && dx && dw && dbias && dz, SSV_BAD_SHAPE, "cm_head_bwd: null argument");
+static int cm_head_bwd_run(const char* name, bool len, const float* x, const float* w, const float* bias, const float* labels, const float* amean,
+                           const float* gscale, float slope, float* dx, float* dw, float* dbias, float* dz, int B, int C, int T, const int* live,
+                           ssv_stream_t stream) {
+  SSV_CHECK(B > 0 && C > 0 && T > 0, SSV_BAD_SHAPE, "%s: need B, C, T > 0, got B=%d C=%d T=%d", name, B, C, T);
+  SSV_CHECK(C <= CM_MAX_C && T <= (1 << 26), SSV_BAD_SHAPE, "%s: C=%d exceeds the %d channels the head is built for (or T=%d exceeds 2^26)", name, C, CM_MAX_C, T);
+  SSV_CHECK(x && w && bias && labels && amean && gscale && dx && dw && dbias && dz && (!len || live), SSV_BAD_SHAPE, "%s: null argument", name);
   hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(cm_head_bwd_kernel, dim3(B), dim3(256), 0, st, x, w, bias, labels, amean, gscale, slope, dx, dz, B, C, T);
-  SSV_TRY(ssv_check_launch("cm_head_bwd"));
+  if (len)
+    hipLaunchKernelGGL(cm_head_bwd_kernel<true>, dim3(B), dim3(256), 0, st, x, w, bias, labels, amean, gscale, slope, dx, dz, B, C, T, live);
+  else
+    hipLaunchKernelGGL(cm_head_bwd_kernel<false>, dim3(B), dim3(256), 0, st, x, w, bias, labels, amean, gscale, slope, dx, dz, B, C, T, live);
+  SSV_TRY(ssv_check_launch(name));
   hipLaunchKernelGGL(cm_head_bwd_params_kernel, dim3(1), dim3(64), 0, st, (const float*)dz, amean, dw, dbias, B, C);
   return ssv_check_launch("cm_head_bwd_params");
+}
+
+extern "C" int ssv_cm_head_fwd(const float* x, const float* w, const float* bias, const float* labels, float slope, float* pred, float* amean,
+                               float* per, float* loss, int B, int C, int T, ssv_stream_t stream) {
+  return cm_head_fwd_run("cm_head_fwd", false, x, w, bias, labels, slope, pred, amean, per, loss, B, C, T, nullptr, stream);
+}
+extern "C" int ssv_cm_head_bwd(const float* x, const float* w, const float* bias, const float* labels, const float* amean, const float* gscale,
+                               float slope, float* dx, float* dw, float* dbias, float* dz, int B, int C, int T, ssv_stream_t stream) {
+  return cm_head_bwd_run("cm_head_bwd", false, x, w, bias, labels, amean, gscale, slope, dx, dw, dbias, dz, B, C, T, nullptr, stream);
+}
+extern "C" int ssv_cm_head_fwd_len(const float* x, const float* w, const float* bias, const float* labels, float slope, float* pred, float* amean,
+                                   float* per, float* loss, int B, int C, int T, const int* live, ssv_stream_t stream) {
+  return cm_head_fwd_run("cm_head_fwd_len", true, x, w, bias, labels, slope, pred, amean, per, loss, B, C, T, live, stream);
+}
+extern "C" int ssv_cm_head_bwd_len(const float* x, const float* w, const float* bias, const float* labels, const float* amean, const float* gscale,
+                                   float slope, float* dx, float* dw, float* dbias, float* dz, int B, int C, int T, const int* live,
+                                   ssv_stream_t stream) {
+  return cm_head_bwd_run("cm_head_bwd_len", true, x, w, bias, labels, amean, gscale, slope, dx, dw, dbias, dz, B, C, T, live, stream);
 }
 
 // ---- multi-tensor Adam with L2 weight decay and AMSGrad ---------------------------------------------------------------------

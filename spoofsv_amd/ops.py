@@ -812,6 +812,27 @@ def avg_pool1d(x, k):
     return AvgPoolFn.apply(x, int(k))
 
 
+class MaskColsFn(torch.autograd.Function):
+    """y = x with the columns at or past ``live`` zeroed (``ssv_mask_cols`` on a copy); linear, so its backward is itself."""
+
+    @staticmethod
+    def forward(ctx, x, live):
+        y = _c(_dev(x, "masked activation")).clone()
+        _mask_cols(y, y.shape[1] * y.shape[2], live)
+        ctx.live = live
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        return MaskColsFn.apply(gy, ctx.live), None
+
+
+def mask_cols(x, live):
+    """``x`` (B, C, L) with the columns at or past the live length (an ``ops.Live``) exactly zero, and the gradient masked the same way:
+    what a column-mixing operator (a kernel-3 convolution) needs in front of it when the batch is padded to a bucket width."""
+    return x if live is None else MaskColsFn.apply(x, live)
+
+
 def grad_penalty(g, lam):
     return GradPenaltyFn.apply(g, lam)[0]
 
@@ -823,7 +844,7 @@ class CmHeadFn(torch.autograd.Function):
     through the loss: ``pred`` is returned for reporting and scoring and carries no gradient."""
 
     @staticmethod
-    def forward(ctx, x, w, bias, labels, slope):
+    def forward(ctx, x, w, bias, labels, slope, live):
         x = _c(_dev(x, "countermeasure head input"))
         if x.dim() != 3 or w.numel() != x.shape[1] or bias.numel() != 1:
             raise RuntimeError("cm_head: x must be (B, C, T) with a (1, C, 1) weight and a 1-element bias, got %s, %s, %s"
@@ -831,8 +852,12 @@ class CmHeadFn(torch.autograd.Function):
         B, C, T = x.shape
         wc, bc = _c(w), _c(bias)
         pred = torch.empty((B,), dtype=_F32, device=x.device)
+        if live is not None and live.mult != 1:
+            raise RuntimeError("cm_head: the live width is one device int (ops.Live with mult = 1)")
+        # (live: the ssv_cm_head_*_len entries, the same kernels reading the width when they run)
+        name, tail = ("ssv_cm_head_fwd", ()) if live is None else ("ssv_cm_head_fwd_len", (live.ptr(),))
         if labels is None:
-            _lib.call("ssv_cm_head_fwd", _p(x), _p(wc), _p(bc), None, float(slope), _p(pred), None, None, None, B, C, T, _stream())
+            _lib.call(name, _p(x), _p(wc), _p(bc), None, float(slope), _p(pred), None, None, None, B, C, T, *tail, _stream())
             ctx.mark_non_differentiable(pred)
             return pred
         labels = _c(_dev(labels, "labels")).reshape(-1)
@@ -841,9 +866,9 @@ class CmHeadFn(torch.autograd.Function):
         amean = torch.empty((B, C), dtype=_F32, device=x.device)
         per = torch.empty((B,), dtype=_F32, device=x.device)
         loss = torch.empty((1,), dtype=_F32, device=x.device)
-        _lib.call("ssv_cm_head_fwd", _p(x), _p(wc), _p(bc), _p(labels), float(slope), _p(pred), _p(amean), _p(per), _p(loss), B, C, T, _stream())
+        _lib.call(name, _p(x), _p(wc), _p(bc), _p(labels), float(slope), _p(pred), _p(amean), _p(per), _p(loss), B, C, T, *tail, _stream())
         ctx.save_for_backward(x, wc, bc, labels, amean)
-        ctx.slope, ctx.wshape, ctx.bshape = float(slope), w.shape, bias.shape
+        ctx.slope, ctx.wshape, ctx.bshape, ctx.live = float(slope), w.shape, bias.shape, live
         ctx.mark_non_differentiable(pred)
         return loss.view(()), pred
 
@@ -863,17 +888,19 @@ class CmHeadFn(torch.autograd.Function):
         dw = torch.empty((C,), dtype=_F32, device=x.device)
         db = torch.empty((1,), dtype=_F32, device=x.device)
         dz = torch.empty((B,), dtype=_F32, device=x.device)
-        _lib.call("ssv_cm_head_bwd", _p(x), _p(w), _p(bias), _p(labels), _p(amean), _p(_c(gloss)), ctx.slope, _p(dx), _p(dw), _p(db), _p(dz),
-                  B, C, T, _stream())
-        return dx, dw.view(ctx.wshape), db.view(ctx.bshape), None, None
+        name, tail = ("ssv_cm_head_bwd", ()) if ctx.live is None else ("ssv_cm_head_bwd_len", (ctx.live.ptr(),))
+        _lib.call(name, _p(x), _p(w), _p(bias), _p(labels), _p(amean), _p(_c(gloss)), ctx.slope, _p(dx), _p(dw), _p(db), _p(dz),
+                  B, C, T, *tail, _stream())
+        return dx, dw.view(ctx.wshape), db.view(ctx.bshape), None, None, None
 
 
-def cm_head(x, w, bias, labels=None, slope=0.05):
+def cm_head(x, w, bias, labels=None, slope=0.05, live=None):
     """The countermeasure's classifier head on ``x`` (B, C <= 16, T), the output of ln4: ``pred`` (B,) = sigmoid(bias + sum_c w[c]
     mean_t leaky_relu(x, slope)) without labels; with ``labels`` (B,) in {0, 1} (float) ``(loss, pred)``, loss the mean binary
     cross-entropy with the reference's 1e-6 inside the logarithms.  Differentiable once, through ``loss`` (a second-order use raises:
-    the backward is marked ``once_differentiable``); ``pred`` carries no gradient."""
-    return CmHeadFn.apply(x, w, bias, labels, slope)
+    the backward is marked ``once_differentiable``); ``pred`` carries no gradient.  ``live`` (an ``ops.Live``): only the first
+    clamp(live, 1, T) columns of ``x`` count -- a batch padded to a bucket width; the rest may hold anything and gets a zero gradient."""
+    return CmHeadFn.apply(x, w, bias, labels, slope, live)
 
 
 # ------------------------------------------------------------------------------------------- critics: LayerNorm / gate, twice differentiable

@@ -255,9 +255,11 @@ class FusedAdamEx(FusedAdam):
 
 class TrainingSnapshot:
     """Undo for the warm-up iterations of a capture, which train: ``take()`` clones every parameter and buffer of ``modules`` and, for
-    every FusedAdam of ``optimizers``, the moments and the true step count; ``restore()`` writes all of it back INTO THE SAME tensors
+    every FusedAdam of ``optimizers``, the moments (AMSGrad's running maximum included) and the true step count; ``restore()`` writes all of it back INTO THE SAME tensors
     (captured hipGraphs hold their addresses) and re-splits the resident weight planes.
     (The critics' dropout call counter, which the warm-up advances too, is not part of it.)"""
+
+    _MOMENTS = ("exp_avg", "exp_avg_sq", "max_exp_avg_sq")          # the last: FusedAdamEx under amsgrad only
 
     def __init__(self, modules, optimizers):
         self.modules, self.optimizers = list(modules), list(optimizers)
@@ -267,7 +269,7 @@ class TrainingSnapshot:
 
     def take(self):
         self.weights = [t.detach().clone() for t in self._tensors()]
-        self.moments = [{p: (st["exp_avg"].clone(), st["exp_avg_sq"].clone()) for p, st in o.state.items() if "exp_avg" in st}
+        self.moments = [{p: {k: st[k].clone() for k in self._MOMENTS if k in st} for p, st in o.state.items() if "exp_avg" in st}
                         for o in self.optimizers]
         # the true step count: replays advance only the device counter, so the host's is stale once any graph has run
         self.steps = [int(o._step_dev.item()) if o._step_dev is not None else o._steps for o in self.optimizers]
@@ -281,8 +283,10 @@ class TrainingSnapshot:
         for o, saved, steps in zip(self.optimizers, self.moments, self.steps):
             for p, st in o.state.items():
                 if "exp_avg" in st:
-                    for key, s in zip(("exp_avg", "exp_avg_sq"), saved.get(p, (None, None))):
-                        st[key].zero_() if s is None else st[key].copy_(s)       # (no saved moment: the state is the warm-up's)
+                    for key in self._MOMENTS:
+                        if key in st:
+                            s = saved.get(p, {}).get(key)
+                            st[key].zero_() if s is None else st[key].copy_(s)       # (no saved moment: the state is the warm-up's)
             o._steps = steps
             if o._step_dev is not None:
                 o._step_dev.fill_(steps)
