@@ -431,6 +431,35 @@ long ssv_clip_sgd_workspace(int nchunks);
 int ssv_clip_sgd_multi(const ssv_clip_sgd_chunk* chunks, int nchunks, const float* max_norm, int ngroups, float lr, float* norms,
                        const float* loss, float* loss_hist, int hist_len, int* step_dev, void* ws, size_t ws_bytes, ssv_stream_t stream);
 
+/* The speaker-verification test on the device: trial scores, threshold sweep, accept rate.  No workspace: every table is the caller's and
+ * its size follows from the arguments.
+ *
+ * Replaces get_centroids + get_cossim as the tests call them, GE2E/train_speech_embedder.py:151-164 and :244-257 (GE2E/utils.py), in ONE
+ * launch: enr (N, E, D) enrolment embeddings, ver (N, ver_stride, D) verification embeddings of which each speaker's first V rows are used
+ * (test_nospoof scores the first 2*eval_num only), sim (N, V, N) out, cent (N, D) out or NULL: the enrolment centroids enr.mean(1).
+ *   sim[i,v,j] = cos(ver[i,v], cent[j]) + 1e-6                                  for j != i,
+ *   sim[i,v,i] = cos(ver[i,v], (sum_v' ver[i,v'] - ver[i,v]) / (V - 1)) + 1e-6  (the sum over the V rows in use; utils.py:42-43),
+ * cos(a, b) = a.b / (max(|a|, 1e-8) * max(|b|, 1e-8)) as the reference's F.cosine_similarity clamps each norm.  fp32; every sum in a fixed order
+ * that depends on D alone (not on the grid or the run).  Centroids and the speaker's sum are staged in LDS, tiled over j when N * D does
+ * not fit; any size runs.  N < 2, V < 2, E < 1, V > ver_stride or D < 1: -1 before anything is launched. */
+int ssv_sv_trial_scores(const float* enr, const float* ver, float* sim, float* cent, int N, int E, int V, int ver_stride, int D, ssv_stream_t stream);
+/* Replaces the threshold loops of GE2E/train_speech_embedder.py:174-194 (test) and :264-284 (test_nospoof).  sim (N, V, N); thr: DEVICE
+ * array of nthr float32 thresholds (the caller uploads the float32 roundings of 0.01*i + 0.5 once); head / tail: rows of the own-speaker
+ * column that form the genuine / the spoofing half (0, 0: the no-spoof variant, gt_FRR and spoof_rate are then 0).  counts (nthr, 4) int32
+ * OUT: per threshold the trials with sim > thr (strict) over the whole matrix, the own-speaker column, its first `head` rows, its last
+ * `tail` rows.  Then, in float64 and in the reference's operation order, with the host-computed constants den, pos (full sweep) and
+ * hden, hpos (half sweep):
+ *   FAR = (all - own) / (N - 1.0) / den / N,  FRR = (N * pos - own) / den / N,  the FIRST threshold with the smallest |FAR - FRR| (strict
+ *   <, starting from 1.0) wins;  gt_FRR = (N * hpos - own_head) / hden / N,  spoof_rate = own_tail / hden / N at that threshold.
+ * hist (hist_len, 6) float64: row *step_dev % hist_len = (EER = (FAR + FRR) / 2, index of the threshold, FAR, FRR, gt_FRR, spoof_rate),
+ * then *step_dev += 1 (the step_dev convention of ssv_clip_sgd_multi: a replayed hipGraph fills successive rows).  Two launches. */
+int ssv_sv_eer_sweep(const float* sim, int N, int V, const float* thr, int nthr, int head, int tail, double den, double pos, double hden,
+                     double hpos, int* counts, double* hist, int hist_len, int* step_dev, ssv_stream_t stream);
+/* Replaces the body of the spoof-rate pass, GE2E/train_speech_embedder.py:313-321, over a DEVICE stack of nmat matrices (N, V, N):
+ * rates[m] (float32) = trials of the own-speaker column in the last `tail` rows with sim > thres, / float(tail) / N.  The comparison is
+ * float32 against the float32 rounding of the threshold, as the reference's `mat > thres` compares a float32 matrix with a Python float. */
+int ssv_sv_accept_rate(const float* sim_stack, int nmat, int N, int V, int tail, float thres, float* rates, ssv_stream_t stream);
+
 /* ---- Vocoder and spectrogram front end ------------------------------------------------
  * Replaces the CPU tail of synthesis, synthesize.py:138-147 / generate_test_utterances.py:128-139
  * (`librosa.core.griffinlim(S, n_iter=64, hop_length, win_length)`, `signal.lfilter([1], [1, -PREEMPH], y)`, peak

@@ -5,7 +5,9 @@
 (:43-49 with GE2E/utils.py:16-55).  The LSTM stack, the projection and the loss run in libssv_hip.so, forward (what
 BASELINE.json's north_star asks) and backward (one iteration of GE2E/train_speech_embedder.py:70-86
 through ``train_iteration``, which ends in torch's own clip_grad_norm_ and SGD; ``GE2ETrainStep``, the iteration on a corpus held
-on the device, runs those too in libssv_hip.so: ``ClipSGD``, and ``tisv_batch_gather`` for the batch).  State-dict keys equal the
+on the device, runs those too in libssv_hip.so: ``ClipSGD``, and ``tisv_batch_gather`` for the batch).  The verification test around the
+embedder (GE2E/train_speech_embedder.py:112-322: trial scores, threshold sweep, spoof rate) has device operators too -- ``sv_trial_scores``,
+``sv_eer_sweep``, ``sv_accept_rate`` -- and ``SvEvalStep`` runs a batch of it on a resident corpus.  State-dict keys equal the
 reference's (``LSTM_stack.weight_ih_l0`` ... ``projection.bias``), so its checkpoints load unchanged.
 
 The reference reads its sizes from a module-global ``hparam`` loaded from config/config.yaml; here they
@@ -453,6 +455,284 @@ class GE2ETrainStep:
 
     def losses(self, n):
         return self.sgd.losses(n)
+
+
+# --------------------------------------------------------------------------------------------- the verification test on the device
+SV_NTHR = 50
+_SV_THR = {}
+
+
+def _sv_thresholds(device):
+    """The sweep's 50 thresholds as ``ge2e_harness.eer_sweep`` builds them for a float32 matrix (the same bits), uploaded once per device."""
+    t = _SV_THR.get(device)
+    if t is None:
+        t = _SV_THR[device] = torch.tensor([0.01 * i + 0.5 for i in range(SV_NTHR)], dtype=torch.float32).to(device)
+    return t
+
+
+def sv_sweep_constants(size_1, es1, spoof=True):
+    """(head, tail, den, pos, hden, hpos) of ``ge2e_harness.eer_sweep``: the host-side divisions of train_speech_embedder.py:174-194 /
+    :264-284, float and integer where the reference has them."""
+    hden, hpos = float(size_1 / 2 - es1 / 2), size_1 // 2 - es1 // 2
+    if spoof:
+        half = (size_1 - es1) // 2
+        return half, half, float(size_1 - es1), size_1 - es1, hden, hpos
+    return 0, 0, hden, hpos, hden, hpos
+
+
+def sv_eval_shapes(N, M, enroll_num, eval_num=None):
+    """(es1, V, V2) of the verification test on batches of N speakers x M utterances: 2*enroll_num enrolment rows, V = M - es1 verification
+    rows, V2 = 2*eval_num of them in the no-spoof test (None without ``eval_num``).  Raises a ``ValueError`` for what the reference asserts
+    (:141, M even) or fails on later: fewer than two speakers (FAR divides by N - 1), no verification half left."""
+    N, M, enroll_num = int(N), int(M), int(enroll_num)
+    if N < 2:
+        raise ValueError("verification test: N = %d, needs at least 2 speakers per batch (FAR divides by N - 1)" % N)
+    if M % 2 != 0:
+        raise ValueError("verification test: M = %d must be even (train_speech_embedder.py:141)" % M)
+    if enroll_num < 1 or 2 * enroll_num >= M:
+        raise ValueError("verification test: 2 * enroll_num = %d enrolment rows of M = %d leave nothing to verify" % (2 * enroll_num, M))
+    es1 = 2 * enroll_num
+    V = M - es1
+    if V < 2:
+        raise ValueError("verification test: M - 2 * enroll_num = %d verification rows, the own-speaker score needs 2" % V)
+    V2 = None
+    if eval_num is not None:
+        V2 = 2 * int(eval_num)
+        if not 2 <= V2 <= V:
+            raise ValueError("verification test: 2 * eval_num = %d must lie in [2, M - 2 * enroll_num = %d]" % (V2, V))
+    return es1, V, V2
+
+
+def _sv_row(row, spoof):
+    best = int(row[1])
+    out = dict(EER=float(row[0]), thres=0.01 * best + 0.5, FAR=float(row[2]), FRR=float(row[3]))
+    if spoof:
+        out["gt_FRR"], out["spoof_rate"] = float(row[4]), float(row[5])
+    return out
+
+
+def sv_trial_scores(e_enr, e_ver, V=None, out=None, cent=None):
+    """``ge2e_harness.cossim_eval(e_ver[:, :V], e_enr.mean(1))`` in one launch (``ssv_sv_trial_scores``): e_enr (N, E, D), e_ver (N, Vs, D)
+    float32 on the device, V (default Vs) rows of every speaker in use -> (N, V, N).  ``out`` / ``cent``: where to write the matrix and the
+    (N, D) centroids (dense float32; the matrix is allocated when absent, the centroids are not kept)."""
+    e_enr, e_ver = _c(e_enr), _c(e_ver)
+    if e_enr.dim() != 3 or e_ver.dim() != 3 or e_enr.shape[0] != e_ver.shape[0] or e_enr.shape[2] != e_ver.shape[2]:
+        raise RuntimeError("sv_trial_scores: need enrolment (N, E, D) and verification (N, V, D) embeddings, got %s and %s" % (tuple(e_enr.shape), tuple(e_ver.shape)))
+    N, E, D = e_enr.shape
+    Vs = e_ver.shape[1]
+    V = Vs if V is None else int(V)
+    if out is None:
+        out = torch.empty((N, max(V, 0), N), dtype=torch.float32, device=e_ver.device)
+    elif not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (N, V, N)):
+        raise RuntimeError("sv_trial_scores: out must be a dense float32 device tensor (%d, %d, %d)" % (N, V, N))
+    if cent is not None and not (cent.is_cuda and cent.dtype == torch.float32 and cent.is_contiguous() and tuple(cent.shape) == (N, D)):
+        raise RuntimeError("sv_trial_scores: cent must be a dense float32 device tensor (%d, %d)" % (N, D))
+    _lib.call("ssv_sv_trial_scores", _p(e_enr), _p(e_ver), _p(out), _p(cent), N, E, V, Vs, D, _stream())
+    return out
+
+
+def _sv_sweep_call(sim, consts, counts, hist, hist_len, step_dev):
+    N, V = sim.shape[0], sim.shape[1]
+    head, tail, den, pos, hden, hpos = consts
+    _lib.call("ssv_sv_eer_sweep", _p(sim), N, V, _p(_sv_thresholds(sim.device)), SV_NTHR, head, tail, den, float(pos), hden, float(hpos),
+              _p(counts), _p(hist), hist_len, _p(step_dev), _stream())
+
+
+def sv_eer_sweep(sim, size_1, es1, spoof=True, return_counts=False):
+    """``ge2e_harness.eer_sweep`` on the device (``ssv_sv_eer_sweep``): the same dict (Python floats; ``thres`` = 0.01 * index + 0.5), one
+    read-back.  ``return_counts``: also the (50, 4) int32 table of accepted trials (all, own column, its head rows, its tail rows)."""
+    _dev(sim, "similarity matrix")
+    if sim.dim() != 3 or sim.shape[0] != sim.shape[2] or sim.dtype != torch.float32:
+        raise RuntimeError("sv_eer_sweep: need a float32 similarity matrix (N, V, N), got %s %s" % (sim.dtype, tuple(sim.shape)))
+    sim = sim.contiguous()
+    counts = torch.zeros((SV_NTHR, 4), dtype=torch.int32, device=sim.device)
+    hist = torch.zeros((1, 6), dtype=torch.float64, device=sim.device)
+    step_dev = torch.zeros((1,), dtype=torch.int32, device=sim.device)
+    _sv_sweep_call(sim, sv_sweep_constants(size_1, es1, spoof), counts, hist, 1, step_dev)
+    out = _sv_row(hist.cpu()[0], spoof)
+    return (out, counts) if return_counts else out
+
+
+def sv_accept_rate(sim_stack, thres, eval_num):
+    """The body of ``ge2e_harness.spoof_rate_at`` over a device stack (nmat, N, V, N) of similarity matrices (``ssv_sv_accept_rate``): per
+    matrix the fraction of own-speaker trials in the last 2*eval_num rows above ``thres``, as Python floats (one read-back)."""
+    _dev(sim_stack, "similarity stack")
+    if sim_stack.dim() != 4 or sim_stack.shape[1] != sim_stack.shape[3] or sim_stack.dtype != torch.float32:
+        raise RuntimeError("sv_accept_rate: need a float32 stack (nmat, N, V, N), got %s %s" % (sim_stack.dtype, tuple(sim_stack.shape)))
+    sim_stack = sim_stack.contiguous()
+    nmat, N, V, _ = sim_stack.shape
+    rates = torch.empty((max(nmat, 1),), dtype=torch.float32, device=sim_stack.device)
+    _lib.call("ssv_sv_accept_rate", _p(sim_stack), nmat, N, V, 2 * int(eval_num), float(thres), _p(rates), _stream())
+    return [float(r) for r in rates.cpu()]
+
+
+class SvEvalStep:
+    """One batch of the verification test (GE2E/train_speech_embedder.py:131-199, and :225-289 when ``eval_num`` is given) on static device
+    buffers: the enrolment and the verification utterances gathered from a corpus held on the device (``corpus`` as for ``GE2ETrainStep``),
+    the embedder's inference forward on each -- the host path's two shapes, (N*es1, frames, nmels) and (N*V, frames, nmels), through the
+    same two C-ABI calls as ``SpeechEmbedder.forward``, so the embeddings are bitwise ``net(enr)`` / ``net(ver)`` on the same rows -- the
+    trial scores and the mixture sweep; with ``eval_num`` also the no-spoof scores (the first 2*eval_num verification rows) and their
+    sweep, from the same embeddings.  Each shape keeps its own LSTM workspace for the life of the step: the weights are scanned and split
+    once per shape (``invalidate()`` after changing them), not once per call as the two shapes alternating through the module's one-entry
+    cache cost; ``SpeechEmbedder.forward`` and that cache are not touched.
+
+    ``graph=True``: ``prepare()`` warms up, captures the batch into one hipGraph (``train.PhasedStep``: one phase, one stream, a plain chain
+    of launches) and resets the history; ``run(rows)`` uploads the (N*M,) row table -- speaker after speaker, M rows each, split here into
+    the two tables -- replays, and copies the mixture matrix into the next slot of ``stack`` (``stack_len`` slots, device to device).
+    ``graph=False`` makes the same calls eagerly.  ``results(n)``: the sweeps' rows of the last n batches in one read-back;
+    ``sims(n)``: their mixture matrices, on the device."""
+
+    def __init__(self, net, corpus, N, M, enroll_num, eval_num=None, graph=True, hist_len=1024, stack_len=None):
+        from .train import PhasedStep
+        self.es1, self.V, self.V2 = sv_eval_shapes(N, M, enroll_num, eval_num)
+        data = getattr(corpus, "data", corpus)
+        if data is None:
+            raise ValueError("SvEvalStep: corpus (the resident (U_total, nmels, frames) tensor, or its holder) is required")
+        _dev(data, "corpus")
+        F, H, layers, P = net.dims
+        if data.dim() != 3 or data.shape[1] != F or data.dtype != torch.float32 or not data.is_contiguous():
+            raise ValueError("SvEvalStep: corpus is %s %s, expected dense float32 (U_total, %d, frames)" % (data.dtype, tuple(data.shape), F))
+        if hist_len < 1 or (stack_len is not None and stack_len < 1):
+            raise ValueError("SvEvalStep: hist_len and stack_len must be positive")
+        self.net, self.corpus, self.N, self.M, self.eval_num = net, data, int(N), int(M), eval_num
+        self.hist_len, self.stack_len = int(hist_len), int(hist_len if stack_len is None else stack_len)
+        T, dev, N = int(data.shape[2]), data.device, self.N
+        lstm = net.LSTM_stack
+        w = [[getattr(lstm, "%s_l%d" % (kind, l)) for l in range(layers)] for kind in ("weight_ih", "weight_hh", "bias_ih", "bias_hh")]
+        self._pw, self._pb = net.projection.weight, net.projection.bias
+        for p in [p for kind in w for p in kind] + [self._pw, self._pb]:
+            _dev(p, "parameter")
+            if p.dtype != torch.float32 or not p.is_contiguous():
+                raise RuntimeError("SvEvalStep needs dense float32 parameters")
+        self._w = w
+        self._ptrs = [_ptr_array(kind) for kind in w]                   # built once: the weights stay where they are
+        self._mode = _lib.precision()
+
+        def f32(*shape):
+            return torch.empty(shape, dtype=torch.float32, device=dev)
+        q = _lib.query
+        # the two sides of the batch: (row table, gathered batch, h_last, embeddings, LSTM dims, LSTM workspace, projection workspace)
+        self._sides = []
+        for Bn in (N * self.es1, N * self.V):
+            dims = (Bn, T, F, H, layers)
+            nb, nb2 = q("ssv_lstm_fwd_workspace", *dims), q("ssv_proj_l2norm_fwd_workspace", Bn, P)
+            self._sides.append(dict(rows=torch.zeros((Bn,), dtype=torch.int32, device=dev), x=f32(Bn, T, F), h=f32(Bn, H), e=f32(Bn, P), dims=dims,
+                                    ws=_ws(nb, dev), nb=nb, ws2=_ws(nb2, dev), nb2=nb2))
+        self._packed = 0                                                # 1 once both workspaces hold the split weight planes
+        self.e_enr, self.e_ver = self._sides[0]["e"].view(N, self.es1, P), self._sides[1]["e"].view(N, self.V, P)
+        self.sim, self.cent = f32(N, self.V, N), f32(N, P)
+        self.sim_nospoof = f32(N, self.V2, N) if self.V2 is not None else None
+        self._consts = sv_sweep_constants(self.M, self.es1, True)
+        self._consts2 = sv_sweep_constants(self.M, self.es1, False)
+        # [0]: the mixture sweep's history, [1]: the no-spoof sweep's -- one tensor, so that results() is one copy
+        self.hist = torch.zeros((2, self.hist_len, 6), dtype=torch.float64, device=dev)
+        self.counts = torch.zeros((2, SV_NTHR, 4), dtype=torch.int32, device=dev)
+        self.step_dev = torch.zeros((2,), dtype=torch.int32, device=dev)
+        self.stack = f32(self.stack_len, N, self.V, N)
+        self.batches = 0                                                # run() calls since prepare(): the host's copy of step_dev
+        _sv_thresholds(dev)                                             # uploaded before any capture
+        # two pinned staging slots and an event after each copy, as GE2ETrainStep keeps them
+        self._rows_host = [torch.empty((N * self.M,), dtype=torch.int32).pin_memory() for _ in range(2)]
+        self._rows_copied = [None, None]
+        self._flip = 0
+        self.stepper = PhasedStep([("graph", self._batch)], graph=graph)
+
+    def _batch(self):
+        if _lib.precision() != self._mode:
+            raise RuntimeError("SvEvalStep: built for arithmetic mode %d, now %d (build a new step after ssv_set_precision)" % (self._mode, _lib.precision()))
+        st, P = _stream(), self._pw.shape[0]
+        for s in self._sides:
+            Bn, T, F, H, layers = s["dims"]
+            tisv_batch_gather(self.corpus, s["rows"], s["x"])
+            _lib.call("ssv_lstm_fwd_cached", _p(s["x"]), *self._ptrs, _p(s["h"]), Bn, T, F, H, layers, _p(s["ws"]), s["nb"], self._packed, st)
+            _lib.call("ssv_proj_l2norm_fwd", _p(s["h"]), _p(self._pw), _p(self._pb), _p(s["e"]), None, Bn, H, P, _p(s["ws2"]), s["nb2"], st)
+        self._packed = 1
+        sv_trial_scores(self.e_enr, self.e_ver, out=self.sim, cent=self.cent)
+        _sv_sweep_call(self.sim, self._consts, self.counts[0], self.hist[0], self.hist_len, self.step_dev[0:1])
+        if self.sim_nospoof is not None:
+            sv_trial_scores(self.e_enr, self.e_ver, V=self.V2, out=self.sim_nospoof)
+            _sv_sweep_call(self.sim_nospoof, self._consts2, self.counts[1], self.hist[1], self.hist_len, self.step_dev[1:2])
+
+    def _reset(self):
+        self.step_dev.zero_()
+        self.hist.zero_()
+        self.batches = 0
+
+    def prepare(self):
+        """Warm up and capture (``graph=True``; one-shot).  Afterwards the history is empty and its counters are zero."""
+        if not self.stepper.use_graph or self.stepper.plan is not None:
+            return self
+        self.stepper.prepare()
+        self._reset()
+        torch.cuda.synchronize()
+        return self
+
+    def release(self):
+        self.stepper.release()
+        return self
+
+    def invalidate(self):
+        """The embedder's weights changed: the next (eager) batch scans and splits them again.  A captured step must be released first."""
+        if self.stepper.plan is not None:
+            raise RuntimeError("SvEvalStep.invalidate: release() the captured batch first; its replay assumes the split weight planes it was captured with")
+        self._packed = 0
+
+    def load(self, rows_host):
+        """Put the batch's (N*M,) row table (host integers, validated here against the corpus) into the two static device tables."""
+        rows = torch.as_tensor(rows_host).reshape(-1)
+        if rows.numel() != self.N * self.M or rows.is_floating_point():
+            raise ValueError("SvEvalStep: the row table must hold N*M = %d integers, got %s %s" % (self.N * self.M, rows.dtype, tuple(rows.shape)))
+        if int(rows.min()) < 0 or int(rows.max()) >= self.corpus.shape[0]:
+            raise ValueError("SvEvalStep: row table entries must lie in [0, %d), got [%d, %d]" % (self.corpus.shape[0], int(rows.min()), int(rows.max())))
+        rows = rows.reshape(self.N, self.M)
+        self._flip ^= 1
+        host, ev = self._rows_host[self._flip], self._rows_copied[self._flip]
+        if ev is not None:
+            ev.synchronize()
+        n_enr = self.N * self.es1
+        host[:n_enr].view(self.N, self.es1).copy_(rows[:, :self.es1])
+        host[n_enr:].view(self.N, self.V).copy_(rows[:, self.es1:])
+        self._sides[0]["rows"].copy_(host[:n_enr], non_blocking=True)
+        self._sides[1]["rows"].copy_(host[n_enr:], non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record()
+        self._rows_copied[self._flip] = ev
+
+    def run(self, rows_host=None):
+        """One batch on ``rows_host`` (None: on the tables already on the device).  Returns the mixture matrix's slot in ``stack``."""
+        if rows_host is not None:
+            self.load(rows_host)
+        self.stepper.run()
+        slot = self.stack[self.batches % self.stack_len]
+        slot.copy_(self.sim)
+        self.batches += 1
+        return slot
+
+    def results(self, n):
+        """The last ``n`` batches' sweeps, oldest first, in one read-back: a list of ``eer_sweep(spoof=True)`` dicts, each with the
+        no-spoof sweep's dict under ``"nospoof"`` when the step has an ``eval_num``."""
+        if n == 0:
+            return []
+        if not 0 < n <= min(self.batches, self.hist_len):
+            raise ValueError("SvEvalStep.results(%d): %d batches run, the history keeps %d" % (n, self.batches, self.hist_len))
+        hist = self.hist.cpu()
+        out = []
+        for k in range(self.batches - n, self.batches):
+            r = _sv_row(hist[0, k % self.hist_len], True)
+            if self.sim_nospoof is not None:
+                r["nospoof"] = _sv_row(hist[1, k % self.hist_len], False)
+            out.append(r)
+        return out
+
+    def sims(self, n=None):
+        """The mixture matrices of the last ``n`` batches (default: all since ``prepare()``), oldest first: a device tensor (n, N, V, N)."""
+        n = self.batches if n is None else n
+        if not 0 < n <= min(self.batches, self.stack_len):
+            raise ValueError("SvEvalStep.sims(%s): %d batches run, the stack keeps %d" % (n, self.batches, self.stack_len))
+        if self.batches <= self.stack_len:
+            return self.stack[self.batches - n:self.batches]
+        idx = torch.tensor([k % self.stack_len for k in range(self.batches - n, self.batches)], device=self.stack.device)
+        return self.stack.index_select(0, idx)
 
 
 # --------------------------------------------------------------------------------------------- multi-GPU (SURVEY 8e, GE2E row)

@@ -5,7 +5,9 @@ loading, the enrollment/verification bookkeeping and the threshold sweep are hos
 ``preprocess_tisv`` is ``GE2E/data_preprocess.py`` with its librosa pass on the device (``spoofsv_amd.sv_frontend``),
 ``preprocess_tisv_synthetic`` the same for ``GE2E/synthetic_data_preprocess.py`` (voiced intervals instead of one trimmed span), and
 ``spoof_evaluation`` the in-memory form of ``test`` for features that never touched a disk.  ``ResidentSpeakerCorpus`` holds the
-training corpus on the device and draws the loader's batches as row tables (``train`` with ``cfg["train"]["resident"]``).
+training corpus on the device and draws the loader's batches as row tables (``train`` with ``cfg["train"]["resident"]``); with
+``cfg["test"]["resident"]`` the tests run on a resident test corpus too, scores and sweep in libssv_hip.so (``ge2e.SvEvalStep``), and ``evaluate``
+is the three of them -- ``test``, ``test_nospoof``, ``spoof_rate_at`` -- in one pass.
 
 Configuration is a plain dict with the fields of ``GE2E/config/config.yaml`` (``default_config()``), instead of the
 reference's module-global ``hparam`` object.
@@ -18,7 +20,8 @@ import numpy as np
 import torch
 from torch.utils.data import DataLoader, Dataset
 
-from .ge2e import GE2ELoss, GE2ETrainStep, SpeechEmbedder, tisv_batch_gather, train_iteration
+from .ge2e import (GE2ELoss, GE2ETrainStep, SpeechEmbedder, SvEvalStep, sv_accept_rate, sv_eer_sweep, sv_eval_shapes, sv_trial_scores, tisv_batch_gather,
+                   train_iteration)
 
 
 def default_config():
@@ -76,6 +79,22 @@ class _SpeakerRows(Dataset):
 
     def __getitem__(self, idx):
         return torch.from_numpy(self.offsets[idx] + np.random.randint(0, self.counts[idx], self.utter_num))
+
+
+class _SpeakerTestRows(Dataset):
+    """The index-only twin of ``SpeakerDatasetPreprocessed(path, M)`` (shuffle=False, the test loader): whatever ``idx`` is, the item makes
+    the ONE random call the host dataset makes -- ``random.sample`` of one out of the speaker list (data_load.py:73) -- and returns that
+    speaker's first M global utterance rows.  No file is opened."""
+
+    def __init__(self, offsets, utter_num):
+        self.offsets, self.utter_num = offsets, utter_num
+        self.speakers = list(range(len(offsets)))
+
+    def __len__(self):
+        return len(self.speakers)
+
+    def __getitem__(self, idx):
+        return torch.from_numpy(self.offsets[random.sample(self.speakers, 1)[0]] + np.arange(self.utter_num, dtype=np.int64))
 
 
 class _RowBatches:
@@ -141,6 +160,18 @@ class ResidentSpeakerCorpus:
         ``torch`` / ``numpy`` seeds select the same speakers and utterances.  Every ``iter()`` of the result is one epoch; an item is the
         batch's (N*M,) int32 table of global utterance rows, speaker after speaker."""
         return _RowBatches(DataLoader(_SpeakerRows(self.offsets, self.counts, M), batch_size=N, shuffle=True, num_workers=0, drop_last=True))
+
+    def test_batches(self, N, M):
+        """The row tables of ``DataLoader(SpeakerDatasetPreprocessed(path, M), batch_size=N, shuffle=True, drop_last=True)``, the loader of
+        ``test`` / ``test_nospoof``, with exactly its random stream: a real ``DataLoader`` with the same arguments (``num_workers=0``) over
+        ``_SpeakerTestRows``, so the same ``random`` / ``torch`` seeds select the same speakers.  The host dataset ignores the index it is given
+        and draws the speaker itself, so a speaker may repeat within a batch; an item is the speaker's FIRST M utterances.  A speaker file
+        with fewer than M utterances raises a ``ValueError`` naming it here (the host loader fails there, inside ``torch.stack``)."""
+        short = [(n, c) for n, c in zip(self.file_list, self.counts) if c < M]
+        if short:
+            raise ValueError("ResidentSpeakerCorpus.test_batches: %s holds %d utterances, the test takes the first M = %d of every speaker"
+                             % (os.path.join(self.path, short[0][0]), short[0][1], M))
+        return _RowBatches(DataLoader(_SpeakerTestRows(self.offsets, M), batch_size=N, shuffle=True, num_workers=0, drop_last=True))
 
     def gather(self, rows_dev, out):
         """``out[b, t, f] = data[rows_dev[b], f, t]`` on the device (``ssv_tisv_batch_gather``)."""
@@ -310,10 +341,110 @@ def _load(cfg, model_path, device):
     return net.eval()
 
 
+def _resident_epochs(cfg, net, enroll_num, eval_num, device, per_epoch=None):
+    """The batches of ``_verification_batches`` on a corpus held on the device: ``ResidentSpeakerCorpus.test_batches`` draws the loader's
+    row tables, one ``SvEvalStep`` (replayed unless cfg["test"]["graph"] is False) embeds, scores and sweeps.  Nothing is read back per
+    batch: with ``per_epoch(e, results, sims)`` the epoch's sweeps are read once at its end, without it nothing is read here at all.
+    Returns (step, batches per epoch)."""
+    te = cfg["test"]
+    sv_eval_shapes(te["N"], te["M"], enroll_num, eval_num)
+    corpus = ResidentSpeakerCorpus(cfg["data"]["test_path"], device)
+    batches = corpus.test_batches(te["N"], te["M"])
+    total = max(1, te["epochs"] * len(batches))
+    step = SvEvalStep(net, corpus, te["N"], te["M"], enroll_num, eval_num, graph=te.get("graph", True), hist_len=total, stack_len=total).prepare()
+    for e in range(te["epochs"]):
+        nb = 0
+        for rows in batches:
+            step.run(rows)
+            nb += 1
+        if per_epoch is not None and nb:
+            per_epoch(e, step.results(nb), step.sims(nb))
+    return step, len(batches)
+
+
+def _epoch_average(per_epoch, n):
+    return sum(sum(v) / len(v) for v in per_epoch.values()) / n
+
+
+@torch.no_grad()
+def _test_resident(cfg, model_path, enroll_num):
+    device = torch.device(cfg["device"])
+    net = _load(cfg, model_path, device)
+    save = cfg["test"].get("save_simmat", True)
+    if save:
+        os.makedirs(cfg["save_simmat_dir"], exist_ok=True)
+    per_epoch_eer, per_epoch_spoof = {}, {}
+
+    def per_epoch(e, results, sims):
+        if save:
+            host = sims.cpu()
+        for b, r in enumerate(results):
+            if save:
+                torch.save(host[b].clone(), os.path.join(cfg["save_simmat_dir"], "simmat_e{}_b{}".format(e + 1, b + 1)))
+            print("\nEER : %0.4f (thres:%0.4f)" % (r["EER"], r["thres"]))
+            per_epoch_eer.setdefault(e, []).append(r["EER"])
+            per_epoch_spoof.setdefault(e, []).append(r["spoof_rate"])
+    step, _ = _resident_epochs(cfg, net, enroll_num, None, device, per_epoch)
+    test.last_step = step
+    n = cfg["test"]["epochs"]
+    avg_eer, avg_spoof = _epoch_average(per_epoch_eer, n), _epoch_average(per_epoch_spoof, n)
+    print("\n EER across {0} epochs: {1:.4f}".format(n, avg_eer))
+    print("\n Spoof rate across {0} epochs: {1:.4f}".format(n, avg_spoof))
+    return avg_eer, avg_spoof
+
+
+@torch.no_grad()
+def _test_nospoof_resident(cfg, model_path, enroll_num, eval_num):
+    device = torch.device(cfg["device"])
+    net = _load(cfg, model_path, device)
+    per_epoch_thres = {}
+
+    def per_epoch(e, results, sims):
+        for r in results:
+            r = r["nospoof"]
+            print("\nEER : %0.4f (thres:%0.4f, FAR:%0.4f, FRR:%0.4f)" % (r["EER"], r["thres"], r["FAR"], r["FRR"]))
+            per_epoch_thres.setdefault(e, []).append(r["thres"])
+    _resident_epochs(cfg, net, enroll_num, eval_num, device, per_epoch)
+    avg = _epoch_average(per_epoch_thres, cfg["test"]["epochs"])
+    print("\n Average threshold: ", avg)
+    return avg
+
+
+@torch.no_grad()
+def evaluate(cfg, model_path, enroll_num, eval_num):
+    """The whole ``__main__`` of train_speech_embedder.py:309-322 -- ``test``, ``test_nospoof``, then the spoof rate at the averaged
+    no-spoof threshold -- in ONE pass over a corpus held on the device: every epoch's batches are drawn once, the mixture sweep and the
+    no-spoof sweep run on the same embeddings (``SvEvalStep`` with ``eval_num``), and the spoof rate at the threshold comes from the
+    mixture matrices the step holds (``sv_accept_rate``).  Two read-backs in all (the sweeps' history, the accept rates), no disk.
+    Returns dict(EER, spoof_rate_at_eer, threshold, spoof_rate), each averaged as the three functions average.
+
+    NOT draw for draw the reference's two-pass sequence: there ``test_nospoof`` draws batches of its own after ``test`` has drawn its, so
+    its threshold is measured on other speakers' draws than the matrices it is applied to.  Here both sweeps see the same batches; the
+    figures are those of the same experiment, not the same random numbers."""
+    device = torch.device(cfg["device"])
+    net = _load(cfg, model_path, device)
+    step, nb = _resident_epochs(cfg, net, enroll_num, eval_num, device)
+    n = cfg["test"]["epochs"]
+    results = step.results(step.batches)
+    by_epoch = [results[e * nb:(e + 1) * nb] for e in range(n)] if nb else []
+
+    def avg(get):
+        return sum(sum(get(r) for r in ep) / len(ep) for ep in by_epoch) / n
+    threshold = avg(lambda r: r["nospoof"]["thres"])
+    evaluate.last_step = step
+    return dict(EER=avg(lambda r: r["EER"]), spoof_rate_at_eer=spoof_rate_at(cfg, threshold, eval_num, sims=step.sims()), threshold=threshold,
+                spoof_rate=avg(lambda r: r["spoof_rate"]))
+
+
 @torch.no_grad()
 def test(cfg, model_path, enroll_num):
     """train_speech_embedder.py:112-203: EER and spoof rate of the mixture test; the similarity matrices are saved for
-    the later spoof-rate pass exactly as the reference saves them.  Returns (avg_EER, avg_spoof_rate)."""
+    the later spoof-rate pass exactly as the reference saves them.  Returns (avg_EER, avg_spoof_rate).
+    cfg["test"]["resident"] = True (absent by default) runs the test from a corpus held on the device (``SvEvalStep``; cfg["test"]["graph"],
+    default True there, selects replay): same lines, printed at the end of each epoch, same return values; the matrices are written only
+    when cfg["test"].get("save_simmat", True), and the step that holds them on the device (``sims()``) is left in ``test.last_step``."""
+    if cfg["test"].get("resident", False):
+        return _test_resident(cfg, model_path, enroll_num)
     device = torch.device(cfg["device"])
     net = _load(cfg, model_path, device)
     os.makedirs(cfg["save_simmat_dir"], exist_ok=True)
@@ -335,7 +466,10 @@ def test(cfg, model_path, enroll_num):
 
 @torch.no_grad()
 def test_nospoof(cfg, model_path, enroll_num, eval_num):
-    """train_speech_embedder.py:205-297: threshold at the EER of the genuine-only test.  Returns the average threshold."""
+    """train_speech_embedder.py:205-297: threshold at the EER of the genuine-only test.  Returns the average threshold.
+    cfg["test"]["resident"] = True: from a corpus held on the device, as ``test``."""
+    if cfg["test"].get("resident", False):
+        return _test_nospoof_resident(cfg, model_path, enroll_num, eval_num)
     device = torch.device(cfg["device"])
     net = _load(cfg, model_path, device)
     per_epoch = {}
@@ -349,9 +483,13 @@ def test_nospoof(cfg, model_path, enroll_num, eval_num):
     return avg
 
 
-def spoof_rate_at(cfg, thres, eval_num):
+def spoof_rate_at(cfg, thres, eval_num, sims=None):
     """train_speech_embedder.py:311-321: fraction of the last 2*eval_num verification trials of each speaker accepted at
-    the no-spoof EER threshold, over the saved similarity matrices."""
+    the no-spoof EER threshold, over the saved similarity matrices -- or, with ``sims``, over that device stack (nmat, N, V, N) of
+    matrices (``SvEvalStep.sims()``; ``sv_accept_rate``), without the disk."""
+    if sims is not None:
+        rates = sv_accept_rate(sims, thres, eval_num)
+        return sum(rates) / len(rates)
     N, rates = cfg["test"]["N"], []
     for k in sorted(os.listdir(cfg["save_simmat_dir"])):
         mat = torch.load(os.path.join(cfg["save_simmat_dir"], k)) > thres
@@ -535,12 +673,13 @@ def preprocess_tisv_synthetic(cfg, speakers, front_end=None, max_intervals=16):
 
 
 @torch.no_grad()
-def spoof_evaluation(cfg, net, enrol, genuine, spoof):
+def spoof_evaluation(cfg, net, enrol, genuine, spoof, device_scoring=False):
     """The mixture test of ``test`` (train_speech_embedder.py:112-203) on features held in memory: ``enrol`` (N, ke, 2, frames, nmels),
     ``genuine`` (N, kg, ...) and ``spoof`` (N, ks, ...) straight from ``TisvFrontEnd`` (kg == ks, as the sweep's halves assume), the
     spoofing utterances never written to disk.  Per speaker the slices are laid out as ``speaker<N>.npy`` has them (enrolment, then
     genuine, then spoof), embedded, compared (``cossim_eval``) and swept (``eer_sweep(spoof=True)``).  Returns the sweep's dict plus
-    the similarity matrix under "sim"."""
+    the similarity matrix under "sim".  ``device_scoring=True`` compares and sweeps in libssv_hip.so instead (``sv_trial_scores``,
+    ``sv_eer_sweep``): the same dict, one read-back."""
     N = enrol.shape[0]
     if not (genuine.shape[0] == N and spoof.shape[0] == N and genuine.shape[1] == spoof.shape[1]):
         raise ValueError("spoof_evaluation: need the same speakers on all three sides and as many genuine as spoofing utterances")
@@ -550,8 +689,12 @@ def spoof_evaluation(cfg, net, enrol, genuine, spoof):
     size_1 = es1 + ver.shape[1]
     e_enr = net(enrol.reshape(N * es1, fr, nm).float().contiguous()).reshape(N, es1, -1)
     e_ver = net(ver.reshape(N * (size_1 - es1), fr, nm).float().contiguous()).reshape(N, size_1 - es1, -1)
-    sim = cossim_eval(e_ver, e_enr.mean(dim=1))
-    out = eer_sweep(sim, size_1, es1, spoof=True)
+    if device_scoring:
+        sim = sv_trial_scores(e_enr, e_ver)
+        out = sv_eer_sweep(sim, size_1, es1, spoof=True)
+    else:
+        sim = cossim_eval(e_ver, e_enr.mean(dim=1))
+        out = eer_sweep(sim, size_1, es1, spoof=True)
     out["sim"] = sim
     return out
 
