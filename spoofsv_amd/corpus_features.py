@@ -111,10 +111,8 @@ class CorpusFeatureExtractor:
         if self._arena is None or self._arena.numel() < need:
             total = _total_bytes(d)                                         # corpus_feature_bytes(B, n_max, cfg, orig_sr)
             self._arena = None                                              # the old arena's memory counts as free below
-            free = torch.cuda.mem_get_info(self.device)[0] + torch.cuda.memory_reserved(self.device) - torch.cuda.memory_allocated(self.device)
-            if total > free:
-                raise RuntimeError("CorpusFeatureExtractor on (B=%d, n_max=%d) waveforms needs %d bytes of device memory (%.1f GB), %d are free: "
-                                   "run fewer utterances per batch" % (d["B"], d["n_max"], total, total / 2.0 ** 30, free))
+            ops.require_free_bytes(total, self.device, "CorpusFeatureExtractor on (B=%d, n_max=%d) waveforms needs" % (d["B"], d["n_max"]),
+                                   "run fewer utterances per batch")
             self._arena = torch.empty((need,), dtype=_F32, device=self.device)
             self.nbytes = 4 * need
         out, off = {}, 0

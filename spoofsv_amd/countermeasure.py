@@ -38,7 +38,7 @@ import torch
 from . import _lib, gradarena, ops
 from .critic import _Disc
 from .ops import _p, _stream
-from .train import FusedAdamEx, PhasedStep, TrainingSnapshot
+from .train import BucketedReplay, FusedAdamEx, PhasedStep, StagedUpload
 
 CM_RATE = 16000                 # spoof_conv1d.py:45,48
 POOLS = {"lin": (8, 4), "mel": (2, 2)}          # discriminator.py:104,108 / :64,68: the two AvgPool1d of CmLinDisc / CmMelDisc
@@ -263,14 +263,10 @@ def cm_resident_bytes(n_items, frames, rows, free=None):
     two tables, the labels and theirs.  With ``free`` (bytes of free device memory): a ``RuntimeError`` naming both figures when the
     corpus does not fit."""
     need = 4 * int(rows) * max(1, int(frames)) + 12 * int(n_items) + 16 * int(n_items)
-    if free is not None and need > free:
-        raise RuntimeError("CmResidentCorpus: %d items (%d frames of %d bins) need %d bytes of device memory (%.1f GB), %d are free: "
-                           "train from the wav files instead (resident=False)" % (n_items, frames, rows, need, need / 2.0 ** 30, free))
+    if free is not None:
+        ops.require_free_bytes(need, None, "CmResidentCorpus: %d items (%d frames of %d bins) need" % (n_items, frames, rows),
+                               "train from the wav files instead (resident=False)", free=free)
     return need
-
-
-def _free_bytes(device):
-    return torch.cuda.mem_get_info(device)[0] + torch.cuda.memory_reserved(device) - torch.cuda.memory_allocated(device)
 
 
 class CmResidentCorpus:
@@ -363,7 +359,7 @@ class CmResidentCorpus:
 
     def _allocate(self, n, rows, frames, min_width):
         self.n, self.rows, self.min_width = int(n), int(rows), int(min_width)
-        self.bytes = cm_resident_bytes(self.n, frames, rows, _free_bytes(self.device))
+        self.bytes = cm_resident_bytes(self.n, frames, rows, ops.free_bytes(self.device))
         dev = self.device
         self.arena = torch.zeros((max(1, frames * rows),), dtype=torch.float32, device=dev)
         self.lens, self.offs = np.zeros((self.n,), dtype=np.int32), np.zeros((self.n,), dtype=np.int64)
@@ -473,16 +469,20 @@ class _Bucket:
         self.x = torch.zeros((B, rows, width), dtype=torch.float32, device=device)
         self.y = torch.zeros((B,), dtype=torch.float32, device=device)
         self.live = torch.tensor([width, 1], dtype=torch.int32, device=device)
+        self.live_upload = StagedUpload(self.live)
         self.loss = torch.zeros((1,), dtype=torch.float32, device=device)
         self.stepper = None
 
+    def release(self):
+        self.stepper.release()
 
-class CmBucketedStep:
+
+class CmBucketedStep(BucketedReplay):
     """Training iterations (main_spoof_conv1d.py:84-90) on batches of a ``CmResidentCorpus``, replayed from one hipGraph per width bucket.
     A full batch whose width fits a bucket is gathered into the bucket's static buffer (zero-padded there by the gather), its width L and
     ``head_width(L)`` are written to two device ints, and the captured iteration -- zero_grad, ``model.loss(x, y, live)``, backward, Adam
     -- is replayed: ``_Disc.trunk(live=)`` and the ``_len`` head make it compute what the unpadded batch would.  One ``train.PhasedStep``
-    per bucket, captured on the first batch that reaches it; its warm-up iterations are undone (``train.TrainingSnapshot``).  A batch wider
+    per bucket, captured on the first batch that reaches it; its warm-up iterations are undone (``train.BucketedReplay``).  A batch wider
     than every bucket, a batch of another size than ``corpus.batch_size`` (the partial last one) and a batch whose head width would be 0
     run eagerly, as ``train`` runs them without buckets.  Gradients live in a ``gradarena.GradArena``: every bucket's graph and every
     eager step hand the optimizer the same addresses.  ``opt``: ``FusedAdamEx(capturable=True)``.  Dropout draws from the device
@@ -490,24 +490,13 @@ class CmBucketedStep:
     ``capture_seconds``.  ``step`` returns the iteration's loss as a 1-element device tensor (valid until the bucket's next step)."""
 
     def __init__(self, model, opt, corpus, width_buckets):
-        if not getattr(opt, "capturable", False):
-            raise ValueError("CmBucketedStep needs FusedAdamEx(capturable=True)")
+        super().__init__(opt, "FusedAdamEx")
         self.model, self.opt, self.corpus = model, opt, corpus
         self.buckets = check_width_buckets(width_buckets)
         self.params = [p for p in model.parameters() if p.requires_grad]
         self.arena = gradarena.GradArena([("all", [[p] for p in self.params])])
-        self.steps = {}
-        self.replays = self.eager = self.captures = 0
-        self.capture_seconds = 0.0
-        self.last_bucket = None
-        self._live_host = self._live_copied = None          # a pinned pair of ints, made with the first replay
 
-    def close(self):
-        """Drop every captured graph and detach the gradient arena from the model."""
-        for st in self.steps.values():
-            if st.stepper is not None:
-                st.stepper.release()
-        self.steps = {}
+    def _release_arena(self):
         self.arena.release()
 
     def bucket_of(self, idx):
@@ -529,24 +518,9 @@ class CmBucketedStep:
         return loss_out
 
     def _set_live(self, st, L):
-        if self._live_host is None:
-            self._live_host = torch.empty((2,), dtype=torch.int32).pin_memory()
-        if self._live_copied is not None:
-            self._live_copied.synchronize()            # the previous copy out of the pinned pair has run (long since, as a rule)
-        self._live_host[0], self._live_host[1] = int(L), head_width(self.corpus.feat_type, L)
-        st.live.copy_(self._live_host, non_blocking=True)
-        self._live_copied = torch.cuda.Event()
-        self._live_copied.record()
-
-    def _capture(self, st):
-        t0 = _time.perf_counter()
-        torch.cuda.synchronize()
-        snapshot = TrainingSnapshot([self.model], [self.opt]).take()          # the warm-up iterations train: undone below
-        st.stepper = PhasedStep([("graph", lambda: self._iteration(st.x, st.y, st.live, st.loss))], graph=True).prepare()
-        torch.cuda.synchronize()
-        snapshot.restore()
-        self.capture_seconds += _time.perf_counter() - t0
-        self.captures += 1
+        host = st.live_upload.host()
+        host[0], host[1] = int(L), head_width(self.corpus.feat_type, L)
+        st.live_upload.send()
 
     def step(self, rows, row0, idx):
         """One iteration on the items ``idx`` = the host copy of ``rows[row0 : row0 + len(idx)]`` (``corpus.rows_of`` an order)."""
@@ -555,13 +529,13 @@ class CmBucketedStep:
             self.eager += 1
             sp = self.corpus.gather(rows, row0, idx)
             return self._iteration(sp[self.corpus.key], sp["data_2"], None)
-        st = self.steps.get(bucket)
-        if st is None:
-            st = self.steps[bucket] = _Bucket(self.corpus.batch_size, self.corpus.rows, bucket, self.corpus.device)
+        st = self.steps.get(bucket) or _Bucket(self.corpus.batch_size, self.corpus.rows, bucket, self.corpus.device)
         self.corpus.gather_into(st.x, rows, row0, st.y)
         self._set_live(st, self.corpus.width(idx))
-        if st.stepper is None:
-            self._capture(st)
+        if st.stepper is None:          # captured on this batch, in the static buffers just filled; registered once the capture has succeeded
+            st.stepper = self._captured([self.model], [self.opt], lambda: PhasedStep(
+                [("graph", lambda: self._iteration(st.x, st.y, st.live, st.loss))], graph=True).prepare())
+            self.steps[bucket] = st
         st.stepper.run()
         self.replays += 1
         return st.loss
@@ -664,7 +638,7 @@ def train(cfg, source, feat_type="lin", save_dir="./checkpoints/cm", resume=None
     finally:
         counters = dict(replays=0, eager=done, captures=0, capture_seconds=0.0)
         if stepper is not None:
-            counters = dict(replays=stepper.replays, eager=stepper.eager, captures=stepper.captures, capture_seconds=stepper.capture_seconds)
+            counters = stepper.stats()
             stepper.close()
     return dict(model=model, optimizer=opt, epoch=epoch, global_iteration=global_iteration, losses=losses, checkpoints=saved, **counters)
 

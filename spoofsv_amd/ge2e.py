@@ -23,6 +23,7 @@ import torch.nn as nn
 
 from . import _lib
 from .ops import _c, _dev, _p, _stream, _ws
+from .train import PhasedStep, StagedUpload, TrainingSnapshot
 
 
 def _ptr_array(tensors):
@@ -239,16 +240,13 @@ class ClipSGD:
         self._max_norm = (ctypes.c_float * len(self.groups))(*[mn for _, mn in self.groups])
         self._key = None
         self._table = None
-        self._flip = 0
 
     def _alloc(self, device):
         assert ctypes.sizeof(_lib.ClipSgdChunk) == 32
         cap = sum((p.numel() + _SGD_PIECE - 1) // _SGD_PIECE for params, _ in self.groups for p in params)
-        # Two pinned tables used alternately with an event after each copy, as FusedAdam keeps them: a rebuild (gradient addresses move
-        # between eager iterations of the autograd path) must not overwrite a pinned table whose asynchronous copy has not run yet.
-        self._host = [torch.empty((cap, 4), dtype=torch.int64).pin_memory() for _ in range(2)]
-        self._copied = [None, None]
+        # (a rebuild refills the table: gradient addresses move between eager iterations of the autograd path)
         self._table = torch.empty((cap, 4), dtype=torch.int64, device=device)
+        self._upload = StagedUpload(self._table)
         self._nb = _lib.query("ssv_clip_sgd_workspace", cap)
         self._ws = _ws(self._nb, device)
         self.norms = torch.zeros((len(self.groups),), dtype=torch.float32, device=device)
@@ -274,15 +272,8 @@ class ClipSGD:
             raise RuntimeError("ClipSGD under capture: parameters or gradients are not those of the last eager call; bind static gradient buffers and warm up first")
         if key != self._key:
             arr = self._rows(live)
-            self._flip ^= 1
-            host, ev = self._host[self._flip], self._copied[self._flip]
-            if ev is not None:
-                ev.synchronize()
-            host[:len(arr)].copy_(arr)
-            self._table.copy_(host, non_blocking=True)
-            ev = torch.cuda.Event()
-            ev.record()
-            self._copied[self._flip] = ev
+            self._upload.host()[:len(arr)].copy_(arr)
+            self._upload.send()
             self._nchunks = len(arr)
             self._key = key
         return self._table, self._nchunks
@@ -319,6 +310,36 @@ class ClipSGD:
         return [float(hist[(steps - n + i) % self.hist_len]) for i in range(n)]
 
 
+# What the steps on a resident corpus share (GE2ETrainStep, SvEvalStep; ``step``: the caller's name, for the messages).
+def _resident_data(corpus, step):
+    """The corpus tensor of ``corpus`` (the tensor itself, or an object with ``data`` holding it), on the device."""
+    data = getattr(corpus, "data", corpus)
+    if data is None:
+        raise ValueError("%s: corpus (the resident (U_total, nmels, frames) tensor, or its holder) is required" % step)
+    return _dev(data, "corpus")
+
+
+def _lstm_weights(net, others, step):
+    """The embedder's LSTM weights as lists per kind (w_ih, w_hh, b_ih, b_hh), layer by layer, and their pointer arrays -- built once: the
+    weights stay where they are -- after checking that they, the projection's and ``others`` are dense float32 device parameters."""
+    w = [[getattr(net.LSTM_stack, "%s_l%d" % (kind, l)) for l in range(net.dims[2])] for kind in ("weight_ih", "weight_hh", "bias_ih", "bias_hh")]
+    for p in [p for kind in w for p in kind] + [net.projection.weight, net.projection.bias] + list(others):
+        _dev(p, "parameter")
+        if p.dtype != torch.float32 or not p.is_contiguous():
+            raise RuntimeError("%s needs dense float32 parameters" % step)
+    return w, [_ptr_array(kind) for kind in w]
+
+
+def _row_table(rows_host, n, n_corpus, step):
+    """The (N*M,) row table ``rows_host`` (host integers) as a flat tensor, validated against a corpus of ``n_corpus`` rows."""
+    rows = torch.as_tensor(rows_host).reshape(-1)
+    if rows.numel() != n or rows.is_floating_point():
+        raise ValueError("%s: the row table must hold N*M = %d integers, got %s %s" % (step, n, rows.dtype, tuple(rows.shape)))
+    if int(rows.min()) < 0 or int(rows.max()) >= n_corpus:
+        raise ValueError("%s: row table entries must lie in [0, %d), got [%d, %d]" % (step, n_corpus, int(rows.min()), int(rows.max())))
+    return rows
+
+
 class GE2ETrainStep:
     """One iteration of GE2E/train_speech_embedder.py:65-86 on static device buffers, nothing of it on the host: the batch gathered from a
     corpus held on the device (``corpus``: a float32 device tensor (U_total, nmels, frames), or an object with ``data`` holding one, such
@@ -332,11 +353,7 @@ class GE2ETrainStep:
     back.  The buffers are sized for the arithmetic mode (``ssv_set_precision``) in force at construction; running in another raises."""
 
     def __init__(self, net, ge2e_loss, N, M, frames, lr, graph=True, corpus=None, hist_len=1024):
-        from .train import PhasedStep
-        data = getattr(corpus, "data", corpus)
-        if data is None:
-            raise ValueError("GE2ETrainStep: corpus (the resident (U_total, nmels, frames) tensor, or its holder) is required")
-        _dev(data, "corpus")
+        data = _resident_data(corpus, "GE2ETrainStep")
         F, H, layers, P = net.dims
         if data.dim() != 3 or data.shape[1] != F or data.shape[2] != frames:
             raise ValueError("GE2ETrainStep: corpus is %s, expected (U_total, %d, %d)" % (tuple(data.shape), F, frames))
@@ -344,14 +361,8 @@ class GE2ETrainStep:
             raise ValueError("GE2ETrainStep: the GE2E loss needs M >= 2 utterances per speaker")
         self.net, self.ge2e_loss, self.N, self.M, self.frames, self.corpus = net, ge2e_loss, int(N), int(M), int(frames), data
         Bn, T, dev = self.N * self.M, self.frames, data.device
-        lstm = net.LSTM_stack
-        self._w = [[getattr(lstm, "%s_l%d" % (kind, l)) for l in range(layers)] for kind in ("weight_ih", "weight_hh", "bias_ih", "bias_hh")]
+        self._w, w_ptrs = _lstm_weights(net, [ge2e_loss.w, ge2e_loss.b], "GE2ETrainStep")
         self._pw, self._pb = net.projection.weight, net.projection.bias
-        params = [p for kind in self._w for p in kind] + [self._pw, self._pb, ge2e_loss.w, ge2e_loss.b]
-        for p in params:
-            _dev(p, "parameter")
-            if p.dtype != torch.float32 or not p.is_contiguous():
-                raise RuntimeError("GE2ETrainStep needs dense float32 parameters")
 
         def f32(*shape):
             return torch.empty(shape, dtype=torch.float32, device=dev)
@@ -375,11 +386,8 @@ class GE2ETrainStep:
                 p.grad = g
         self._pw.grad, self._pb.grad = self._dpw, self._dpb
         ge2e_loss.w.grad, ge2e_loss.b.grad = self._dw1.reshape(()), self._db1.reshape(())
-        self._ptrs = [_ptr_array(kind) for kind in self._w] + [_ptr_array(grads) for grads in self._g]
-        # two pinned staging slots and an event after each copy: the host must not overwrite a table that a copy in flight still reads
-        self._rows_host = [torch.empty((Bn,), dtype=torch.int32).pin_memory() for _ in range(2)]
-        self._rows_copied = [None, None]
-        self._flip = 0
+        self._ptrs = w_ptrs + [_ptr_array(grads) for grads in self._g]
+        self._rows_upload = StagedUpload(self.rows)
         self.sgd = ClipSGD([(list(net.parameters()), 3.0), (list(ge2e_loss.parameters()), 1.0)], lr, hist_len)
         self.loss = self._loss1[0]
         self.stepper = PhasedStep([("graph", self._iteration)], graph=graph)
@@ -407,12 +415,10 @@ class GE2ETrainStep:
 
     def prepare(self):
         """Warm up and capture (``graph=True``; one-shot): afterwards every parameter is what it was before and no loss is in the history."""
-        from .train import TrainingSnapshot
         if not self.stepper.use_graph or self.stepper.plan is not None:
             return self
-        snap = TrainingSnapshot([self.net, self.ge2e_loss], []).take()
-        self.stepper.prepare()
-        snap.restore()
+        with TrainingSnapshot([self.net, self.ge2e_loss], []):
+            self.stepper.prepare()
         self.sgd.step_dev.zero_()               # the warm-up's iterations are not part of the history
         self.sgd.loss_hist.zero_()
         self.net.invalidate()
@@ -425,20 +431,9 @@ class GE2ETrainStep:
 
     def load(self, rows_host):
         """Put the (N*M,) row table (host integers, validated here against the corpus) into the static device buffer."""
-        rows = torch.as_tensor(rows_host).reshape(-1)
-        if rows.numel() != self.rows.numel() or rows.is_floating_point():
-            raise ValueError("GE2ETrainStep: the row table must hold N*M = %d integers, got %s %s" % (self.rows.numel(), rows.dtype, tuple(rows.shape)))
-        if int(rows.min()) < 0 or int(rows.max()) >= self.corpus.shape[0]:
-            raise ValueError("GE2ETrainStep: row table entries must lie in [0, %d), got [%d, %d]" % (self.corpus.shape[0], int(rows.min()), int(rows.max())))
-        self._flip ^= 1
-        host, ev = self._rows_host[self._flip], self._rows_copied[self._flip]
-        if ev is not None:
-            ev.synchronize()
-        host.copy_(rows)
-        self.rows.copy_(host, non_blocking=True)
-        ev = torch.cuda.Event()
-        ev.record()
-        self._rows_copied[self._flip] = ev
+        rows = _row_table(rows_host, self.rows.numel(), self.corpus.shape[0], "GE2ETrainStep")
+        self._rows_upload.host().copy_(rows)
+        self._rows_upload.send()
 
     def run(self, rows_host=None):
         """One iteration on ``rows_host`` (None: on the table already in the device buffer).  Returns the loss as a device scalar, valid
@@ -583,12 +578,8 @@ class SvEvalStep:
     ``sims(n)``: their mixture matrices, on the device."""
 
     def __init__(self, net, corpus, N, M, enroll_num, eval_num=None, graph=True, hist_len=1024, stack_len=None):
-        from .train import PhasedStep
         self.es1, self.V, self.V2 = sv_eval_shapes(N, M, enroll_num, eval_num)
-        data = getattr(corpus, "data", corpus)
-        if data is None:
-            raise ValueError("SvEvalStep: corpus (the resident (U_total, nmels, frames) tensor, or its holder) is required")
-        _dev(data, "corpus")
+        data = _resident_data(corpus, "SvEvalStep")
         F, H, layers, P = net.dims
         if data.dim() != 3 or data.shape[1] != F or data.dtype != torch.float32 or not data.is_contiguous():
             raise ValueError("SvEvalStep: corpus is %s %s, expected dense float32 (U_total, %d, frames)" % (data.dtype, tuple(data.shape), F))
@@ -597,26 +588,22 @@ class SvEvalStep:
         self.net, self.corpus, self.N, self.M, self.eval_num = net, data, int(N), int(M), eval_num
         self.hist_len, self.stack_len = int(hist_len), int(hist_len if stack_len is None else stack_len)
         T, dev, N = int(data.shape[2]), data.device, self.N
-        lstm = net.LSTM_stack
-        w = [[getattr(lstm, "%s_l%d" % (kind, l)) for l in range(layers)] for kind in ("weight_ih", "weight_hh", "bias_ih", "bias_hh")]
+        self._w, self._ptrs = _lstm_weights(net, [], "SvEvalStep")
         self._pw, self._pb = net.projection.weight, net.projection.bias
-        for p in [p for kind in w for p in kind] + [self._pw, self._pb]:
-            _dev(p, "parameter")
-            if p.dtype != torch.float32 or not p.is_contiguous():
-                raise RuntimeError("SvEvalStep needs dense float32 parameters")
-        self._w = w
-        self._ptrs = [_ptr_array(kind) for kind in w]                   # built once: the weights stay where they are
         self._mode = _lib.precision()
 
         def f32(*shape):
             return torch.empty(shape, dtype=torch.float32, device=dev)
         q = _lib.query
         # the two sides of the batch: (row table, gathered batch, h_last, embeddings, LSTM dims, LSTM workspace, projection workspace)
+        # (the row tables are views of ONE (N*M,) device table, enrolment rows first, verification rows after: one upload serves both)
         self._sides = []
-        for Bn in (N * self.es1, N * self.V):
+        self.rows = torch.zeros((N * self.M,), dtype=torch.int32, device=dev)
+        for rows in self.rows.split((N * self.es1, N * self.V)):
+            Bn = rows.numel()
             dims = (Bn, T, F, H, layers)
             nb, nb2 = q("ssv_lstm_fwd_workspace", *dims), q("ssv_proj_l2norm_fwd_workspace", Bn, P)
-            self._sides.append(dict(rows=torch.zeros((Bn,), dtype=torch.int32, device=dev), x=f32(Bn, T, F), h=f32(Bn, H), e=f32(Bn, P), dims=dims,
+            self._sides.append(dict(rows=rows, x=f32(Bn, T, F), h=f32(Bn, H), e=f32(Bn, P), dims=dims,
                                     ws=_ws(nb, dev), nb=nb, ws2=_ws(nb2, dev), nb2=nb2))
         self._packed = 0                                                # 1 once both workspaces hold the split weight planes
         self.e_enr, self.e_ver = self._sides[0]["e"].view(N, self.es1, P), self._sides[1]["e"].view(N, self.V, P)
@@ -631,10 +618,7 @@ class SvEvalStep:
         self.stack = f32(self.stack_len, N, self.V, N)
         self.batches = 0                                                # run() calls since prepare(): the host's copy of step_dev
         _sv_thresholds(dev)                                             # uploaded before any capture
-        # two pinned staging slots and an event after each copy, as GE2ETrainStep keeps them
-        self._rows_host = [torch.empty((N * self.M,), dtype=torch.int32).pin_memory() for _ in range(2)]
-        self._rows_copied = [None, None]
-        self._flip = 0
+        self._rows_upload = StagedUpload(self.rows)
         self.stepper = PhasedStep([("graph", self._batch)], graph=graph)
 
     def _batch(self):
@@ -679,24 +663,11 @@ class SvEvalStep:
 
     def load(self, rows_host):
         """Put the batch's (N*M,) row table (host integers, validated here against the corpus) into the two static device tables."""
-        rows = torch.as_tensor(rows_host).reshape(-1)
-        if rows.numel() != self.N * self.M or rows.is_floating_point():
-            raise ValueError("SvEvalStep: the row table must hold N*M = %d integers, got %s %s" % (self.N * self.M, rows.dtype, tuple(rows.shape)))
-        if int(rows.min()) < 0 or int(rows.max()) >= self.corpus.shape[0]:
-            raise ValueError("SvEvalStep: row table entries must lie in [0, %d), got [%d, %d]" % (self.corpus.shape[0], int(rows.min()), int(rows.max())))
-        rows = rows.reshape(self.N, self.M)
-        self._flip ^= 1
-        host, ev = self._rows_host[self._flip], self._rows_copied[self._flip]
-        if ev is not None:
-            ev.synchronize()
-        n_enr = self.N * self.es1
+        rows = _row_table(rows_host, self.N * self.M, self.corpus.shape[0], "SvEvalStep").reshape(self.N, self.M)
+        host, n_enr = self._rows_upload.host(), self.N * self.es1
         host[:n_enr].view(self.N, self.es1).copy_(rows[:, :self.es1])
         host[n_enr:].view(self.N, self.V).copy_(rows[:, self.es1:])
-        self._sides[0]["rows"].copy_(host[:n_enr], non_blocking=True)
-        self._sides[1]["rows"].copy_(host[n_enr:], non_blocking=True)
-        ev = torch.cuda.Event()
-        ev.record()
-        self._rows_copied[self._flip] = ev
+        self._rows_upload.send()
 
     def run(self, rows_host=None):
         """One batch on ``rows_host`` (None: on the tables already on the device).  Returns the mixture matrix's slot in ``stack``."""

@@ -22,6 +22,7 @@ from torch.utils.data import DataLoader, Dataset
 
 from .ge2e import (GE2ELoss, GE2ETrainStep, SpeechEmbedder, SvEvalStep, sv_accept_rate, sv_eer_sweep, sv_eval_shapes, sv_trial_scores, tisv_batch_gather,
                    train_iteration)
+from .ops import require_free_bytes
 
 
 def default_config():
@@ -142,10 +143,8 @@ class ResidentSpeakerCorpus:
         self.total = int(self.counts.sum())
         self.bytes = 4 * self.total * self.nmels * self.frames
         if self.device.type == "cuda":
-            free = torch.cuda.mem_get_info(self.device)[0] + torch.cuda.memory_reserved(self.device) - torch.cuda.memory_allocated(self.device)
-            if self.bytes > free:
-                raise RuntimeError("ResidentSpeakerCorpus(%s): %d utterances of (%d, %d) need %d bytes of device memory (%.1f GB), %d are free: "
-                                   "train from the host loader instead" % (path, self.total, self.nmels, self.frames, self.bytes, self.bytes / 2.0 ** 30, free))
+            require_free_bytes(self.bytes, self.device, "ResidentSpeakerCorpus(%s): %d utterances of (%d, %d) need" % (path, self.total, self.nmels, self.frames),
+                               "train from the host loader instead")
         self.data = torch.empty((self.total, self.nmels, self.frames), dtype=torch.float32, device=self.device)
         for name, off, cnt in zip(self.file_list, self.offsets, self.counts):            # one speaker at a time: no second host copy of the corpus
             utters = np.ascontiguousarray(np.load(os.path.join(path, name)), dtype=np.float32)

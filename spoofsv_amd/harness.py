@@ -567,8 +567,7 @@ def ordinary_train(train_step, train_pattern, cfg, spec_dir=None, resume_checkpo
 
 
 def _bucket_stats(b):
-    return {"replays": b.replays, "eager": b.eager, "captures": b.captures, "capture_seconds": b.capture_seconds,
-            "pool_bytes": dict(b.pool_bytes)}
+    return dict(b.stats(), pool_bytes=dict(b.pool_bytes))
 
 
 def adversarial_train(train_step, train_pattern, cfg, spec_dir=None, resume_checkpoints=None, current_time=None):
@@ -712,10 +711,9 @@ def _adversarial_setup(train_step, cfg, dev, model, disc, src, gaw, ck, rank, wo
         sp = _pad_to_global(sp, world)
         return [sp[k].to(dev) for k in train.KINDS[kind].keys]
     first = pick(next(iter(src.source)))          # shapes only; the prefetching iterator starts with the training loop
-    snapshot = train.TrainingSnapshot([model, disc], [opt_syn, opt_disc]).take()
-    stepper = train.AdversarialGraphStep(kind, model, disc, opt_syn, opt_disc, first, gaw, cfg["LAMBDA"], ddp_syn, ddp_disc, graph=graph,
-                                         coeff_seed=cfg.get("SEED", 0))
-    snapshot.restore()
+    with train.TrainingSnapshot([model, disc], [opt_syn, opt_disc]):
+        stepper = train.AdversarialGraphStep(kind, model, disc, opt_syn, opt_disc, first, gaw, cfg["LAMBDA"], ddp_syn, ddp_disc, graph=graph,
+                                             coeff_seed=cfg.get("SEED", 0))
     return stepper, opt_syn, opt_disc, pick
 
 

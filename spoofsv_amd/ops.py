@@ -61,6 +61,20 @@ def _ws(nbytes, device):
     return torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=device)
 
 
+def free_bytes(device):
+    """Device memory an allocation can still get: what the driver reports free plus what torch's allocator holds but has not handed out."""
+    return torch.cuda.mem_get_info(device)[0] + torch.cuda.memory_reserved(device) - torch.cuda.memory_allocated(device)
+
+
+def require_free_bytes(need, device, what, advice, free=None):
+    """The refusal before a large allocation: a ``RuntimeError`` naming ``need`` and the free device memory when the first exceeds the
+    second (exactly enough is enough).  ``what`` opens the sentence, verb included ("... needs"), ``advice`` ends it.  ``free``: the
+    figure to hold ``need`` against when the caller has it already (default: ``free_bytes(device)``)."""
+    free = free_bytes(device) if free is None else free
+    if need > free:
+        raise RuntimeError("%s %d bytes of device memory (%.1f GB), %d are free: %s" % (what, need, need / 2.0 ** 30, free, advice))
+
+
 class Live:
     """The live length of a stack in a length-masked step (a batch padded to a bucket shape): entry ``index`` of the int32 device tensor
     ``lens``, times ``mult`` (SSRN's upsampled stages).  The kernels read it when they run, so one captured hipGraph serves every batch

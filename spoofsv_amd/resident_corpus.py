@@ -15,7 +15,7 @@ import os
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, ops
 from .ops import _p, _stream
 
 _STAGE_BYTES = 64 << 20          # one pinned staging buffer (there are two): the files of a chunk cross in one copy
@@ -129,10 +129,8 @@ def resident_corpus_bytes(p, device=None):
     device memory when the first exceeds the second -- before anything is allocated."""
     need = p.total_bytes
     if device is not None:
-        free = torch.cuda.mem_get_info(device)[0] + torch.cuda.memory_reserved(device) - torch.cuda.memory_allocated(device)
-        if need > free:
-            raise RuntimeError("CORPUS_RESIDENT: %d items (%s) need %d bytes of device memory (%.1f GB), %d are free: "
-                               "train from the spectrogram cache instead (remove the key)" % (p.n, ", ".join(p.parts), need, need / 2.0 ** 30, free))
+        ops.require_free_bytes(need, device, "CORPUS_RESIDENT: %d items (%s) need" % (p.n, ", ".join(p.parts)),
+                               "train from the spectrogram cache instead (remove the key)")
     return need
 
 

@@ -325,10 +325,8 @@ class WideSynthesizer(_ColumnSynthesizer):
         dims = (batch, text_len, frames, self.d, self.F, U, sum(op.kind == "highway" for op in self.schedule), self.tile)
         need = wide_synth_bytes(*dims)
         if torch.device(device).type == "cuda":
-            free = torch.cuda.mem_get_info(device)[0] + torch.cuda.memory_reserved(device) - torch.cuda.memory_allocated(device)
-            if need > free:
-                raise RuntimeError("WideSynthesizer(batch=%d, text_len=%d, frames=%d) needs %d bytes of device memory (%.1f GB), %d are free: "
-                                   "run fewer items per batch" % (batch, text_len, frames, need, need / 2.0 ** 30, free))
+            ops.require_free_bytes(need, device, "WideSynthesizer(batch=%d, text_len=%d, frames=%d) needs" % (batch, text_len, frames),
+                                   "run fewer items per batch")
         self.nbytes = need
         self.hist = []
         for name, shape, size in _wide_buffers(*dims):

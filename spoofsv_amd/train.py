@@ -14,6 +14,7 @@ import ctypes
 import os
 import contextlib
 import gc
+import time
 from types import SimpleNamespace
 
 import numpy as np
@@ -83,9 +84,7 @@ class FusedAdam(torch.optim.Optimizer):
                                       decoupled_weight_decay=False))
         self.capturable = capturable
         self._table = None
-        self._host_tables = None
-        self._host_flip = 0
-        self._copied = None
+        self._upload = None
         self._key = None
         self._step_dev = None
         self._steps = 0
@@ -140,26 +139,14 @@ class FusedAdam(torch.optim.Optimizer):
         arr = np.array(rows, dtype=np.int64)
         cols = self._COLS
         assert ctypes.sizeof(self._CHUNK_STRUCT) == 8 * cols and arr.shape[1] == cols
-        # Pinned staging buffer + async copy, both allocated once (sized for every parameter): refilling
-        # them is legal while a hipGraph is being captured (the copy becomes a memcpy node).
-        # Two pinned tables used alternately, and an event after each copy: a rebuild (gradient addresses can move between
-        # eager iterations) must not overwrite a pinned table whose asynchronous copy has not executed yet.
-        if self._host_tables is None:
+        # The device table and its staging are allocated once, sized for every parameter: a rebuild (gradient addresses can move
+        # between eager iterations) refills them, also while a hipGraph is being captured (StagedUpload).
+        if self._upload is None:
             cap = sum((p.numel() + _CHUNK - 1) // _CHUNK for g in self.param_groups for p in g["params"])
-            self._host_tables = [torch.empty((cap, cols), dtype=torch.int64).pin_memory() for _ in range(2)]
-            self._copied = [None, None]
             self._table = torch.empty((cap, cols), dtype=torch.int64, device=plist[0].device)
-        self._host_flip ^= 1
-        host, ev = self._host_tables[self._host_flip], self._copied[self._host_flip]
-        capturing = torch.cuda.is_current_stream_capturing()
-        if ev is not None and not capturing:
-            ev.synchronize()
-        host[:len(rows)].copy_(torch.from_numpy(arr))
-        self._table.copy_(host, non_blocking=True)
-        if not capturing:
-            ev = torch.cuda.Event()
-            ev.record()
-            self._copied[self._host_flip] = ev
+            self._upload = StagedUpload(self._table)
+        self._upload.host()[:len(rows)].copy_(torch.from_numpy(arr))
+        self._upload.send()
         self._nchunks = len(rows)
         self._key = key
 
@@ -257,7 +244,9 @@ class TrainingSnapshot:
     """Undo for the warm-up iterations of a capture, which train: ``take()`` clones every parameter and buffer of ``modules`` and, for
     every FusedAdam of ``optimizers``, the moments (AMSGrad's running maximum included) and the true step count; ``restore()`` writes all of it back INTO THE SAME tensors
     (captured hipGraphs hold their addresses) and re-splits the resident weight planes.
-    (The critics' dropout call counter, which the warm-up advances too, is not part of it.)"""
+    (The critics' dropout call counter, which the warm-up advances too, is not part of it.)
+    As a context, ``with TrainingSnapshot(modules, optimizers): <warm up and capture>``, it takes on entry and, on a clean exit, waits
+    for the device and restores; an exception passes through with nothing restored (no graph was made that the state must agree with)."""
 
     _MOMENTS = ("exp_avg", "exp_avg_sq", "max_exp_avg_sq")          # the last: FusedAdamEx under amsgrad only
 
@@ -266,6 +255,19 @@ class TrainingSnapshot:
 
     def _tensors(self):
         return [t for m in self.modules for t in list(m.parameters()) + list(m.buffers())]
+
+    def _sync(self):
+        tensors = self._tensors()
+        if tensors and tensors[0].is_cuda:          # (host modules, the tests': nothing to wait for)
+            torch.cuda.synchronize()
+
+    def __enter__(self):
+        return self.take()
+
+    def __exit__(self, exc_type, exc, tb):
+        if exc_type is None:
+            self._sync()
+            self.restore()
 
     def take(self):
         self.weights = [t.detach().clone() for t in self._tensors()]
@@ -291,8 +293,38 @@ class TrainingSnapshot:
             if o._step_dev is not None:
                 o._step_dev.fill_(steps)
             o.refresh_resident_weights()          # (the copies above bumped the weights' versions: the planes are re-split in place)
-        if tensors and tensors[0].is_cuda:
-            torch.cuda.synchronize()
+        self._sync()
+
+
+class StagedUpload:
+    """The host-to-device path of ONE device tensor ``dst`` that the host rewrites between iterations (a chunk table, a row table, live
+    lengths): ``slots`` pinned buffers of its shape and dtype, used in turn, and one event per slot.  ``host()`` moves to the next slot,
+    waits for that slot's last copy and returns the pinned buffer to fill; ``send()`` copies it to ``dst`` asynchronously on the current
+    stream and records the slot's event behind the copy.  So a refill never overwrites a pinned buffer whose copy has not executed yet
+    (the device would silently get the NEXT table), and with two slots the host waits for the copy before the last, long since run.
+    While the current stream is capturing, the event is neither waited for nor recorded: HIP refuses an event synchronise from a
+    capturing thread (see ``ops.DeferredWgrad._slot``), and the copy becomes a memcpy node of the graph.  The pinned buffers are
+    allocated here, once: a capture cannot allocate them."""
+
+    def __init__(self, dst, slots=2):
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("StagedUpload: run one eager iteration before capturing (staging tables are pinned buffers, "
+                               "which cannot be allocated during a hipGraph capture)")
+        self.dst = dst
+        self._host = [torch.empty(dst.shape, dtype=dst.dtype).pin_memory() for _ in range(slots)]
+        self.events = [torch.cuda.Event() for _ in range(slots)]          # (an event never recorded is waited for at no cost)
+        self._at = 0
+
+    def host(self):
+        self._at = (self._at + 1) % len(self._host)
+        if not torch.cuda.is_current_stream_capturing():
+            self.events[self._at].synchronize()
+        return self._host[self._at]
+
+    def send(self):
+        self.dst.copy_(self._host[self._at], non_blocking=True)
+        if not torch.cuda.is_current_stream_capturing():
+            self.events[self._at].record()
 
 
 # --------------------------------------------------------------------------------------------- data
@@ -757,8 +789,7 @@ class TrainStep:
         # lens: int32 device tensor of the batch's own maxima -- (N_b, T_b) for Text2Mel, (T_b,) for SSRN -- when the batch is padded to a
         # larger shape (BucketedTrainStep): the step then computes what the unpadded batch would (tts.live_lengths)
         self.lens = lens
-        self._lens_host = torch.empty(lens.numel(), dtype=torch.int32).pin_memory() if lens is not None else None     # see set_live_lengths
-        self._lens_copied = None
+        self._lens_upload = StagedUpload(lens) if lens is not None else None     # see set_live_lengths
         # weight gradients of equal-shaped layers batched into one launch per backward segment (ops.DeferredWgrad)
         self.defer = ops.DeferredWgrad() if defer_wgrad else None
         # static: the buffers a captured step reads -- given ones are adopted as they are, else the batch is cloned
@@ -847,14 +878,11 @@ class TrainStep:
         return self
 
     def set_live_lengths(self, need):
-        """Write the batch's own maxima ``need`` into ``lens`` (through a pinned staging buffer, asynchronously) for the next iteration."""
-        if self._lens_copied is not None:
-            self._lens_copied.synchronize()       # the previous asynchronous copy out of the pinned buffer has run (long since, as a rule)
+        """Write the batch's own maxima ``need`` into ``lens`` (``StagedUpload``: asynchronously) for the next iteration."""
+        host = self._lens_upload.host()
         for j, v in enumerate(need):
-            self._lens_host[j] = v
-        self.lens.copy_(self._lens_host, non_blocking=True)
-        self._lens_copied = torch.cuda.Event()
-        self._lens_copied.record()
+            host[j] = v
+        self._lens_upload.send()
 
     def __call__(self, *batch):
         """Run one iteration; with a batch argument, on that batch (copied into the static buffers of a captured step)."""
@@ -929,7 +957,45 @@ def _pad_into(dst, src):
         dst[..., L:].zero_()
 
 
-class BucketedTrainStep:
+class BucketedReplay:
+    """What the bucketed steps share (``BucketedTrainStep``, ``countermeasure.CmBucketedStep``): one captured step per bucket in
+    ``steps`` (anything with ``release()``), made by ``_captured`` on the first batch that reaches the bucket; the counters of
+    ``stats()`` and ``last_bucket`` (None after an eager iteration); ``close()``.  A subclass maps a batch to a bucket (another batch
+    size than the bucket's, or no bucket, means eager), fills the static buffers, runs the iteration, counts ``replays`` / ``eager``
+    and detaches its gradient arena in ``_release_arena``.  ``opt`` must keep its step count on the device (``capturable``)."""
+
+    def __init__(self, opt, needs):
+        if not getattr(opt, "capturable", False):
+            raise ValueError("%s needs %s(capturable=True)" % (type(self).__name__, needs))
+        self.steps = {}
+        self.replays = self.eager = self.captures = 0
+        self.capture_seconds = 0.0
+        self.last_bucket = None
+
+    def _captured(self, modules, optimizers, make):
+        """``make()`` -- warm up and capture a bucket's step -- timed and counted, its training undone: the warm-up iterations train, so
+        weights and optimizer state are put back afterwards, into the same tensors.  A ``make`` that raises counts nothing."""
+        snapshot = TrainingSnapshot(modules, optimizers)
+        snapshot._sync()
+        t0 = time.perf_counter()
+        with snapshot:
+            made = make()
+        self.capture_seconds += time.perf_counter() - t0
+        self.captures += 1
+        return made
+
+    def stats(self):
+        return dict(replays=self.replays, eager=self.eager, captures=self.captures, capture_seconds=self.capture_seconds)
+
+    def close(self):
+        """Drop every captured graph, then detach the gradient arena (``_release_arena``)."""
+        for st in self.steps.values():
+            st.release()
+        self.steps = {}
+        self._release_arena()
+
+
+class BucketedTrainStep(BucketedReplay):
     """Non-adversarial iterations of ragged corpus batches on captured, replayed steps: one ``TrainStep(graph=True)`` per length
     bucket -- (N, T) for ``kind`` "text2mel", (T,) for "ssrn" -- captured on the first batch that falls into it.  A batch runs in the
     smallest bucket that holds its own maxima: it is copied into the bucket's static buffers with the tail columns zeroed, its maxima
@@ -944,8 +1010,7 @@ class BucketedTrainStep:
     ``capture_seconds``; ``pool_bytes[bucket]`` = device memory the capture kept (its activation pool and static buffers)."""
 
     def __init__(self, kind, model, opt, buckets, gaw=None, ddp=None, defer_wgrad=True, batch_size=None):
-        if not getattr(opt, "capturable", False):
-            raise ValueError("BucketedTrainStep needs FusedAdam(capturable=True)")
+        super().__init__(opt, "FusedAdam")
         if kind == "text2mel" and gaw is None:
             raise ValueError("BucketedTrainStep('text2mel') needs the guided-attention weights gaw")
         if ddp is not None and ddp.arena is None:
@@ -958,17 +1023,10 @@ class BucketedTrainStep:
         self.ddp = ddp if ddp is not None else DataParallelRanks(model=model, segmented=False)
         self.defer_wgrad = defer_wgrad
         self.batch_size = batch_size
-        self.steps = {}
-        self.replays = self.eager = self.captures = 0
-        self.capture_seconds = 0.0
         self.pool_bytes = {}
-        self.last_bucket = None
 
-    def close(self):
-        """Drop every captured graph; a gradient arena made here is released from the model."""
-        for st in self.steps.values():
-            st.release()
-        self.steps = {}
+    def _release_arena(self):
+        """A gradient arena made here is released from the model."""
         if self.own_ddp:
             self.ddp.close()
 
@@ -976,25 +1034,14 @@ class BucketedTrainStep:
         return KINDS[self.kind].need(batch)
 
     def _capture(self, bucket, batch):
-        import time
-        dev = batch[0].device
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        lens = torch.tensor(bucket, dtype=torch.int32, device=dev)
+        lens = torch.tensor(bucket, dtype=torch.int32, device=batch[0].device)
         static = [torch.zeros(s, dtype=b.dtype, device=b.device) for s, b in zip(KINDS[self.kind].static_shapes(bucket, batch), batch)]
         for d, b in zip(static, batch):
             _pad_into(d, b)
-        # the capture's warm-up iterations train: weights and optimizer state are put back (into the same tensors) afterwards
-        snapshot = TrainingSnapshot([self.model], [self.opt]).take()
-        st = TrainStep(self.kind, self.model, self.opt, None, self.gaw, self.ddp, graph=True, defer_wgrad=self.defer_wgrad, lens=lens,
-                       static=static).prepare()
-        torch.cuda.synchronize()
-        snapshot.restore()
-        del snapshot
-        self.capture_seconds += time.perf_counter() - t0
-        self.captures += 1
+        st = self._captured([self.model], [self.opt], lambda: TrainStep(
+            self.kind, self.model, self.opt, None, self.gaw, self.ddp, graph=True, defer_wgrad=self.defer_wgrad, lens=lens, static=static).prepare())
         pool = tuple(st.stepper.pool)
-        self.pool_bytes[bucket] = sum(4 * b.numel() if b.dtype != torch.int64 else 8 * b.numel() for b in static) + sum(
+        self.pool_bytes[bucket] = sum(4 * b.numel() if b.dtype != torch.int64 else 8 * b.numel() for b in st.static) + sum(
             seg["total_size"] for seg in torch.cuda.memory_snapshot() if tuple(seg.get("segment_pool_id", ())) == pool)
         self.steps[bucket] = st
         return st
