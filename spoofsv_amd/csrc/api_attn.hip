@@ -12,14 +12,11 @@ extern "C" int ssv_attention_apply(const float* v, long kv_bs, const float* a, i
   g.M = d; g.N = T; g.Kc = N; g.B = B;
   return ssv_launch_gemm_nn(g, (hipStream_t)stream);
 }
-#ifndef SSV_ATTN_FUSED
-#define SSV_ATTN_FUSED 1     // (tuning builds: 0 = two GEMM launches, the softmax kernel and the row copy, as before round 5)
-#endif
 extern "C" int ssv_attention_train_fwd(const float* k, const float* v, long kv_bs, const float* q, long q_bs, float* a, float* r, long r_bs,
                                        int B, int d, int N, int T, ssv_stream_t stream) {
   SSV_CHECK(k && v && q && a && r && B > 0 && d > 0 && N > 0 && T > 0, SSV_BAD_SHAPE, "attention_train_fwd: bad argument");
   hipStream_t st = (hipStream_t)stream;
-  if (SSV_ATTN_FUSED && ssv_attn_fused_ok(B, d, N, T)) return ssv_launch_attn_fwd_fused(k, v, kv_bs, q, q_bs, a, r, r_bs, 0, B, d, N, T, st);
+  if (ssv_attn_fused_ok(B, d, N, T)) return ssv_launch_attn_fwd_fused(k, v, kv_bs, q, q_bs, a, r, r_bs, 0, B, d, N, T, st);
   GemmNN g;                       // scores(b,n,t) = sum_c k(b,c,n) q(b,c,t) / sqrt(d)
   g.A = k; g.sab = kv_bs; g.sam = 1; g.sac = N; g.saj = 0;
   g.X = q; g.sxb = q_bs; g.sxc = T; g.Lx = T;
@@ -33,7 +30,7 @@ extern "C" int ssv_attention_train_fwd(const float* k, const float* v, long kv_b
 extern "C" int ssv_attention_train_fwd_rq(const float* k, const float* v, long kv_bs, const float* q, long q_bs, float* a, float* rq, long rq_bs,
                                           int B, int d, int N, int T, ssv_stream_t stream) {
   SSV_CHECK(k && v && q && a && rq && B > 0 && d > 0 && N > 0 && T > 0 && rq_bs >= (long)2 * d * T, SSV_BAD_SHAPE, "attention_train_fwd_rq: bad argument");
-  if (SSV_ATTN_FUSED && ssv_attn_fused_ok(B, d, N, T)) return ssv_launch_attn_fwd_fused(k, v, kv_bs, q, q_bs, a, rq, rq_bs, 1, B, d, N, T, (hipStream_t)stream);
+  if (ssv_attn_fused_ok(B, d, N, T)) return ssv_launch_attn_fwd_fused(k, v, kv_bs, q, q_bs, a, rq, rq_bs, 1, B, d, N, T, (hipStream_t)stream);
   SSV_TRY(ssv_attention_train_fwd(k, v, kv_bs, q, q_bs, a, rq, rq_bs, B, d, N, T, stream));
   return ssv_copy_rows(q, q_bs, rq + (long)d * T, rq_bs, B, (long)d * T, stream);
 }
@@ -102,7 +99,7 @@ extern "C" int ssv_attention_train_bwd(const float* dr, long dr_bs, const float*
     g.M = d; g.Nc = N; g.B = B; g.Z = B; g.bstep = B;
     return nt_per_batch(g, T, st, fb);
   };
-  if (SSV_ATTN_FUSED && ssv_attn_fused_ok(B, d, N, T)) {
+  if (ssv_attn_fused_ok(B, d, N, T)) {
     // dA, dS (left in ws for dk) and dq in ONE launch
     SSV_TRY(ssv_launch_attn_bwd_fused(dr, dr_bs, da_ext, dq_add, dq_add_bs, k, v, kv_bs, a, dA, dq, dq_bs, B, d, N, T, st));
     SSV_TRY(over_time(dr, dr_bs, a, dv));          // dv(b,c,n) = sum_t dr(b,c,t) a(b,n,t)

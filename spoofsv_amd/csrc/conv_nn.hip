@@ -97,9 +97,7 @@ __global__ __launch_bounds__(256, SSV_NNB_WAVES(KT, WM, NT, EPI, HW)) void gemm_
   }
   // chunks to run: all of K, except that an LSTM entry at its first frame has no h_{t-1} segment (layer 0 riding along: nothing but that segment)
   const int nchunks_all = lstm_l0 ? (x0fold ? xsp + p.perm_h / 32 : p.xsplit) : p.Kpad / 32;
-  const int nchunks_ = (EPI == 1 && p.lstm_D > 0 && lstm_t == 0) ? (lstm_l0 ? (x0fold ? xsp : 0) : p.xsplit) : (EPI == 0 && KT == 1 && p.ksplit > 1) ? p.Kc / 32 : nchunks_all;
-  // (tuning builds, -DSSV_LSTM_ABL: bit 0 = the pre-split wavefront's cells store nothing, bit 1 = its tiles run two chunks; profiles/round6_ge2e_cell_epilogue.txt (6))
-  const int nchunks = (SSV_LSTM_ABL & 2) && XS ? (nchunks_ < 2 ? nchunks_ : 2) : nchunks_;
+  const int nchunks = (EPI == 1 && p.lstm_D > 0 && lstm_t == 0) ? (lstm_l0 ? (x0fold ? xsp : 0) : p.xsplit) : (EPI == 0 && KT == 1 && p.ksplit > 1) ? p.Kc / 32 : nchunks_all;
   const int W = BN + span;
   const int kq = lane >> 4, nq = lane & 15;
 
@@ -195,10 +193,12 @@ __global__ __launch_bounds__(256, SSV_NNB_WAVES(KT, WM, NT, EPI, HW)) void gemm_
   // Not for the branch: hipcc lays an if / else out as two tests in a row, its s_waitcnt bookkeeping then sees a path on which NEITHER form ran, and
   // in front of every chunk's first MFMA it waited for all but the weight fragments' own loads -- i.e. for the input loads issued a few hundred
   // cycles earlier, one exposed round trip per chunk (round 5; the steady / tail split below had removed only the "is there a chunk c + 2" tests).
+  // Only for the tiles where it measured faster in-step (k = 1 tiles -2 %, the 128 x 112 k = 3 tile with the 16-column halo -2.5 %): the 64-row and
+  // 96-column k = 3 tiles and every 54-column-halo tile were equal or up to 15 % SLOWER with it and keep the two-form prefetch.
   const __amdgpu_buffer_rsrc_t rsXr = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(Xb), 0,
       (int)(((long)(p.Kc - 1) * Lrow + (long)(p.Lx - 1) * p.sxn + 1) * 4), 0x00020000);
   auto prefetchX = [&](int ch) {
-    if constexpr (EPI == 0 && SSV_NN_XONE && (KT == 1 || (WM == 2 && NT == 7 && HW == 16))) {
+    if constexpr (EPI == 0 && (KT == 1 || (WM == 2 && NT == 7 && HW == 16))) {
 #pragma unroll
       for (int i = 0; i < 8; ++i) {
         const unsigned so = (unsigned)((ch * 32 + i) * Lrow) * 4u;                // uniform row offset: scalar arithmetic
@@ -228,7 +228,9 @@ __global__ __launch_bounds__(256, SSV_NNB_WAVES(KT, WM, NT, EPI, HW)) void gemm_
         for (int r = 0; r < NX; ++r) rx[r][i] = ssv_buf_f32(rs, voffb[r], so);
       }
     } else if (!ragged || ch + 1 < nchunks) {
-      const bool seg2 = EPI == 1 && X2b && ch >= p.xsplit;                       // (LSTM: the h_{t-1} segment of K)
+      // (convolutions only from here on -- EPI == 1 took a branch above and seg2 is constant false; the terms stay because dropping them changes what
+      // the lambda captures, and with that the register allocation of the k = 3 tiles)
+      const bool seg2 = EPI == 1 && X2b && ch >= p.xsplit;
 #pragma unroll
       for (int i = 0; i < 8; ++i) {
         if constexpr (SSV_NN_XBUF(KT, WM, NT)) {
@@ -469,30 +471,19 @@ __global__ __launch_bounds__(256, SSV_NNB_WAVES(KT, WM, NT, EPI, HW)) void gemm_
         float gte[4];
 #pragma unroll
         for (int r = 0; r < 4; ++r) gte[r] = (F16 ? acc[i][t][r] * us : acc[i][t][r]) + addv[i][r] + rproj[i][t][r];
-#if SSV_LSTM_FAST_CELL
-        // (tuning builds) v_exp_f32 / v_rcp_f32 forms, as the LayerNorm / gate kernels' sigmoid: ~8 instructions per gate instead of ~25 / ~40
+        // v_exp_f32 / v_rcp_f32 forms, as the LayerNorm / gate kernels' sigmoid: ~8 instructions per gate instead of ~25 / ~40 with expf / tanhf / IEEE
+        // division (config 5 10.51 -> 10.16 ms same box; the embeddings' distance from the float oracle 2.6e-7 -> 1.5e-6, bar 2e-5: tanh(x) =
+        // 1 - 2 / (1 + e^2x) is absolute-accurate to ~1e-7, not relative, for |x| << 1)
         const float gi = __builtin_amdgcn_rcpf(1.f + __expf(-gte[0])), gf = __builtin_amdgcn_rcpf(1.f + __expf(-gte[1]));
         const float gg = 1.f - 2.f * __builtin_amdgcn_rcpf(1.f + __expf(2.f * gte[2])), go = __builtin_amdgcn_rcpf(1.f + __expf(-gte[3]));
-#else
-        const float gi = 1.f / (1.f + expf(-gte[0])), gf = 1.f / (1.f + expf(-gte[1]));
-        const float gg = tanhf(gte[2]), go = 1.f / (1.f + expf(-gte[3]));
-#endif
         const long ci = (long)u * p.N + gn;
         const float cn = (first ? 0.f : gf * cprev[i][t]) + gi * gg;
-#if SSV_LSTM_ABL & 1
-        if (cn == 1234.5678f) cnew[ci] = cn;
-#else
         cnew[ci] = cn;
-#endif
         if (gsave) {
           const long HN = (long)H * p.N;
           gsave[ci] = gi; gsave[HN + ci] = gf; gsave[2 * HN + ci] = gg; gsave[3 * HN + ci] = go;
         }
-#if SSV_LSTM_FAST_CELL
         const float hval = go * (1.f - 2.f * __builtin_amdgcn_rcpf(1.f + __expf(2.f * cn)));
-#else
-        const float hval = go * tanhf(cn);
-#endif
         if (!XS || p.hs_keep_h) Cb[(long)u * p.scm + gn] = hval;
         if constexpr (XS) {
           // the same h, split as its consumers would split it (scale 2^14: |h| < 1), into the planes of (layer, slot t % 2)
@@ -501,12 +492,8 @@ __global__ __launch_bounds__(256, SSV_NNB_WAVES(KT, WM, NT, EPI, HW)) void gemm_
           const _Float16 hl = (_Float16)(hs_ - (float)hh);
           _Float16* ph = reinterpret_cast<_Float16*>(reinterpret_cast<char*>(p.hs_planes) + ((long)lstm_layer * 2 + (lstm_t & 1)) * 2 * p.hs_plane_bytes);
           const long at = ((long)(u >> 3) * p.hs_npad + gn) * 8 + (u & 7);
-#if SSV_LSTM_ABL & 1
-          if (hval == 1234.5678f) { ph[at] = hh; ph[at + p.hs_plane_bytes / 2] = hl; }
-#else
           ph[at] = hh;
           ph[at + p.hs_plane_bytes / 2] = hl;
-#endif
         }
       }
     }
@@ -723,7 +710,7 @@ __global__ __launch_bounds__(256 * NWN, (NWN == 2 && KT == 1) ? 4 : 1) void gemm
   constexpr int A_SLOTS = KT * 4 * BM, X_SLOTS = 4 * WX;
   constexpr int NA = (A_SLOTS + T - 1) / T, NX = (X_SLOTS + T - 1) / T;
   // (the epilogue re-uses the staging memory to park every wave's 16 x (16 NT) blocks for row-contiguous stores, as gemm_nn_bf3_kernel does)
-  constexpr int LDWP = 16 * NT + 4, PARK_U4 = SSV_NNBW_PARK ? (4 * NWN * 16 * LDWP) / 4 : 0;
+  constexpr int LDWP = 16 * NT + 4, PARK_U4 = (4 * NWN * 16 * LDWP) / 4;
   constexpr int STAGE_U4 = 2 * A_SLOTS + 2 * X_SLOTS;
   __shared__ uint4 lds[STAGE_U4 > PARK_U4 ? STAGE_U4 : PARK_U4];
   uint4* Ah = lds;
@@ -896,63 +883,63 @@ __global__ __launch_bounds__(256 * NWN, (NWN == 2 && KT == 1) ? 4 : 1) void gemm
 
   float* __restrict__ Cb = p.C + (long)b * p.scb;
   const float* __restrict__ Rb = p.R ? p.R + (long)b * p.srb : nullptr;
-  if constexpr (SSV_NNBW_PARK) {
-    if (p.scn == 1) {
-      __syncthreads();                                            // every wave is done reading the last chunk's image
-      float* pk = reinterpret_cast<float*>(lds) + wave * 16 * LDWP;
+  if (p.scn == 1) {
+    __syncthreads();                                            // every wave is done reading the last chunk's image
+    float* pk = reinterpret_cast<float*>(lds) + wave * 16 * LDWP;
 #pragma unroll
-      for (int i = 0; i < WM; ++i) {
-        const int rbase = m0 + wm * WM * 16 + i * 16;
+    for (int i = 0; i < WM; ++i) {
+      const int rbase = m0 + wm * WM * 16 + i * 16;
 #pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int gmc = min(rbase + kq * 4 + r, Mt - 1);
-          float add = 0.f;
-          if (p.bias) add += p.bias[gmc];
-          if (p.bias_b) add += p.bias_b[(long)b * p.sbb + gmc];
+      for (int r = 0; r < 4; ++r) {
+        const int gmc = min(rbase + kq * 4 + r, Mt - 1);
+        float add = 0.f;
+        if (p.bias) add += p.bias[gmc];
+        if (p.bias_b) add += p.bias_b[(long)b * p.sbb + gmc];
 #pragma unroll
-          for (int t = 0; t < NT; ++t) pk[(kq * 4 + r) * LDWP + t * 16 + nq] = (F16 ? acc[i][t][r] * us : acc[i][t][r]) + add;
-        }
-        // (the block is private to the wave: its LDS operations complete in order)
+        for (int t = 0; t < NT; ++t) pk[(kq * 4 + r) * LDWP + t * 16 + nq] = (F16 ? acc[i][t][r] * us : acc[i][t][r]) + add;
+      }
+      // (the block is private to the wave: its LDS operations complete in order)
 #pragma unroll
-        for (int it = 0; it < NT; ++it) {
-          const int e = lane + 64 * it;
-          const int row = e / (4 * NT), c4 = e % (4 * NT);
-          const int gm = rbase + row, gn = n0 + wn * NT * 16 + c4 * 4;
-          const f32x4 v = *reinterpret_cast<const f32x4*>(pk + row * LDWP + c4 * 4);
-          if (gm < Mt && gn < p.N) {
-            float* dst = Cb + (long)gm * p.scm + gn;
-            if (gn + 3 < p.N) {
-              f4u o = {v[0], v[1], v[2], v[3]};
-              if (Rb) { const f4u rr = *reinterpret_cast<const f4u*>(Rb + (long)gm * p.srm + gn); o += rr; }
-              *reinterpret_cast<f4u*>(dst) = o;
-            } else {
+      for (int it = 0; it < NT; ++it) {
+        const int e = lane + 64 * it;
+        const int row = e / (4 * NT), c4 = e % (4 * NT);
+        const int gm = rbase + row, gn = n0 + wn * NT * 16 + c4 * 4;
+        const f32x4 v = *reinterpret_cast<const f32x4*>(pk + row * LDWP + c4 * 4);
+        if (gm < Mt && gn < p.N) {
+          float* dst = Cb + (long)gm * p.scm + gn;
+          if (gn + 3 < p.N) {
+            f4u o = {v[0], v[1], v[2], v[3]};
+            if (Rb) { const f4u rr = *reinterpret_cast<const f4u*>(Rb + (long)gm * p.srm + gn); o += rr; }
+            *reinterpret_cast<f4u*>(dst) = o;
+          } else {
 #pragma unroll
-              for (int j = 0; j < 4; ++j) if (gn + j < p.N) dst[j] = v[j] + (Rb ? Rb[(long)gm * p.srm + gn + j] : 0.f);
-            }
+            for (int j = 0; j < 4; ++j) if (gn + j < p.N) dst[j] = v[j] + (Rb ? Rb[(long)gm * p.srm + gn + j] : 0.f);
           }
         }
       }
     }
   }
-  if (!SSV_NNBW_PARK || p.scn != 1) {
+  // (pick_nnb launches this kernel with unit column stride only; the plain form stays compiled in, and as a second test, not an else: either change
+  //  re-schedules the k = 3 instantiations)
+  if (p.scn != 1) {
 #pragma unroll
-  for (int i = 0; i < WM; ++i)
+    for (int i = 0; i < WM; ++i)
 #pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int gm = m0 + wm * WM * 16 + i * 16 + kq * 4 + r;
-      if (gm >= Mt) continue;
-      float add = 0.f;
-      if (p.bias) add += p.bias[gm];
-      if (p.bias_b) add += p.bias_b[(long)b * p.sbb + gm];
+      for (int r = 0; r < 4; ++r) {
+        const int gm = m0 + wm * WM * 16 + i * 16 + kq * 4 + r;
+        if (gm >= Mt) continue;
+        float add = 0.f;
+        if (p.bias) add += p.bias[gm];
+        if (p.bias_b) add += p.bias_b[(long)b * p.sbb + gm];
 #pragma unroll
-      for (int t = 0; t < NT; ++t) {
-        const int gn = n0 + wn * NT * 16 + t * 16 + nq;
-        if (gn >= p.N) continue;
-        float v = (F16 ? acc[i][t][r] * us : acc[i][t][r]) + add;
-        if (Rb) v += Rb[(long)gm * p.srm + gn];
-        Cb[(long)gm * p.scm + gn] = v;
+        for (int t = 0; t < NT; ++t) {
+          const int gn = n0 + wn * NT * 16 + t * 16 + nq;
+          if (gn >= p.N) continue;
+          float v = (F16 ? acc[i][t][r] * us : acc[i][t][r]) + add;
+          if (Rb) v += Rb[(long)gm * p.srm + gn];
+          Cb[(long)gm * p.scm + gn] = v;
+        }
       }
-    }
   }
   if constexpr (XR) {
     if (xr_on) {                                            // (workgroup-uniform) row M - 1: the four k-groups' partial sums of a column, then bias and residual
@@ -1034,18 +1021,18 @@ static int launch_nnb(const GemmNNB& g, hipStream_t st, int smin, int span) {
 
 template <int KT>
 static int pick_nnb(const GemmNNB& g, hipStream_t st, int smin, int span) {
-  {
+  if constexpr (KT == 1) {
     // measured (round-1 tile sweep; in-step re-check: tools/sweep_force.sh): the wide workgroup wins for kernel-size-1 convolutions over long sequences
     // (SSRN's 513-channel layers: 150 -> 205 TFLOP/s); the k=3 layers are as fast or faster on the 4-wave kernel.
     // 128 x 192 tiles (8 waves) are the faster wide shape (513 -> 512 channels: 104 -> 87 us, 256 -> 512: 60 -> 49 us) except
     // when M leaves a nearly empty last row tile (M = 513), where the 16-wave 128 x 448 tile loses less (round-1 sweep)
     // ... and only when the 128 x 192 tiling still gives every CU a workgroup: a single long utterance (the vocoder's DFT
     // at B = 1: 1026 x 1300 x 1024) is 27-56 wide tiles, a fifth of the chip; the cost model below then picks small tiles.
-    if (KT == 1 && !g.epi && !g.perm_h && !g.colstats && !g.row_pair && g.sxn == 1 && g.scn == 1 && g.N >= 1024 && g.M >= 256 && g.Kc >= 256 &&
+    if (!g.epi && !g.perm_h && !g.colstats && !g.row_pair && g.sxn == 1 && g.scn == 1 && g.N >= 1024 && g.M >= 256 && g.Kc >= 256 &&
         (long)ssv_cdiv(g.M, 128) * ssv_cdiv(g.N, 192) * g.B >= 256)
     {
       // M = 128 j + 1 (SSRN's 513 channels): the last row beside the tiles of the 128 x 192 kernel (120.6 -> see DESIGN 4.6) instead of a fifth row tile
-      if (SSV_NNBW_XROW && g.xrow_w && g.M % 128 == 1 && g.Kpad <= 1056 && g.scn == 1 && g.sxn == 1) return launch_nnbw_xrow(g, st, smin, span);
+      if (g.xrow_w && g.M % 128 == 1 && g.Kpad <= 1056 && g.scn == 1 && g.sxn == 1) return launch_nnbw_xrow(g, st, smin, span);
       return (g.M % 128 == 0) ? launch_nnbw<KT, 2, 6, 2>(g, st, smin, span) : launch_nnbw<KT, 2, 7, 4>(g, st, smin, span);
     }
   }

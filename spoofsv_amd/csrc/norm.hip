@@ -19,16 +19,9 @@
 // depths 2, 4, 6, 8 were measured in-step: equal within 1 % -- 4 keeps the hot instantiations at 128 VGPRs (4 waves per SIMD)
 #define LN_PIPE(CPT) ((CPT) < 4 ? (CPT) : 4)
 
-#ifndef SSV_SIGMOID_DIV
-#define SSV_SIGMOID_DIV 0      // (tuning builds: 1 = the IEEE division sequence of rounds 1-4)
-#endif
 // v_rcp_f32 (1 ulp) instead of the IEEE division sequence (two div_scale, rcp, four fma, div_fmas, div_fixup: ten instructions per element)
 __device__ __forceinline__ float sigmoidf_(float v) {
-#if SSV_SIGMOID_DIV
-  return 1.f / (1.f + __expf(-v));
-#else
   return __builtin_amdgcn_rcpf(1.f + __expf(-v));
-#endif
 }
 
 // Sum `v` over the G channel groups of this thread's column. `red` is a [G][16] LDS array.
@@ -939,12 +932,9 @@ __global__ __launch_bounds__(16 * G) void ln_gate_bwd2_kernel(
 }
 
 // Sum the per-workgroup partial rows part[blk][n] in two levels, in a fixed order (bitwise reproducible).
-#ifndef SSV_RED_ROWS
-#define SSV_RED_ROWS 32
-#endif
 // Level 1: workgroup (x, y) folds rows y, y+RED_ROWS, ... into row y IN PLACE (every element of row y is read
 // and written by the same thread, so no other workgroup touches it).  Level 2: out[i] = sum of rows 0..RED_ROWS-1.
-#define RED_ROWS SSV_RED_ROWS
+#define RED_ROWS 32
 // (eight rows in flight per thread and trip at both levels: with two / four these launches were chains of 5 + 16 memory round trips --
 //  11 + 6.4 us per use, eleven uses per training step)
 __global__ __launch_bounds__(256) void reduce_partials_l1_kernel(float* __restrict__ part, int n, int nblk) {

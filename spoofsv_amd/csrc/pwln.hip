@@ -34,7 +34,7 @@ __global__ __launch_bounds__(512, 2) void gemm_pwln_kernel(const PwLn q) {
   // stage one slot each (with 32-channel chunks only waves 0-3 staged while waves 4-7 waited at the barrier), and the staging of chunk c + 1 runs
   // in pieces behind the row blocks' MFMAs of chunk c (tools/probe/ldsdma_ring.hip, profiles/round6_ldsdma_ring_probe.txt: 1.12 -> 0.91 us per
   // 32 channels in the probe's model of this loop; the weight stream itself is not the limit: 0.74 us with nothing else in the loop)
-  constexpr bool K64 = SSV_PWLN_BK64 && WMB == 4 && NT == 4;
+  constexpr bool K64 = WMB == 4 && NT == 4;
   constexpr int KG = K64 ? 8 : 4;                      // k-groups (8 channels each) of a staged chunk
   constexpr int X_SLOTS = KG * BN;                     // 16-byte slots of one chunk: [k-group][column]
   static_assert(X_SLOTS <= 512, "one slot per thread");
@@ -51,7 +51,7 @@ __global__ __launch_bounds__(512, 2) void gemm_pwln_kernel(const PwLn q) {
   // epilogue (round 5): every wave parks a 16-row block row-major and reads it back as 16-byte vectors along the rows, so a store instruction
   // covers four whole 256-byte row pieces instead of 64-byte pieces of 16 rows (what gemm_nn_bf3_kernel's epilogue has done since round 2)
   constexpr int LDWP = BN + 4;
-  __shared__ float park[SSV_PWLN_PARK ? 8 * 16 * LDWP : 1];
+  __shared__ float park[8 * 16 * LDWP];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const unsigned wg = ssv_xcd_order(blockIdx.x + gridDim.x * blockIdx.y, gridDim.x * gridDim.y);
   const int ntile = (int)(wg % gridDim.x), b = (int)(wg / gridDim.x);
@@ -175,10 +175,9 @@ __global__ __launch_bounds__(512, 2) void gemm_pwln_kernel(const PwLn q) {
     prefetch64(min(1, ((nchunks + 1) >> 1) - 1));
   } else {
     commitX(0);
-    if constexpr (SSV_PWLN_ROLL) prefetchXr(min(1, nchunks - 1));
-    else if (nchunks > 1) prefetchX(1);
+    prefetchXr(min(1, nchunks - 1));
   }
-  if constexpr (NSET == 2 && SSV_PWLN_ROLL) {
+  if constexpr (NSET == 2) {
     // two weight-fragment sets, every load unconditional (clamped chunk index, one-path prefetch: see the rolling loop below)
     const int last = nchunks - 1;
     loadA(1, min(1, last));
@@ -192,23 +191,6 @@ __global__ __launch_bounds__(512, 2) void gemm_pwln_kernel(const PwLn q) {
       if (ch + 1 < nchunks) tap(NSET - 1, ch + 1);
       if (ch + 2 < nchunks) commitX(ch + 2);
       prefetchXr(min(ch + 3, last)); loadA(NSET - 1, min(ch + 3, last));
-      __syncthreads();
-    }
-  } else if constexpr (NSET == 2) {
-    if (nchunks > 1) loadA(1, 1);
-    __syncthreads();
-    PW_STAMP(1);
-    for (int ch = 0; ch < nchunks; ch += 2) {
-      tap(0, ch);
-      if (ch + 1 >= nchunks) break;
-      commitX(ch + 1);
-      if (ch + 2 < nchunks) { prefetchX(ch + 2); loadA(0, ch + 2); }
-      __syncthreads();
-      tap(NSET - 1, ch + 1);
-      if (ch + 2 < nchunks) {
-        commitX(ch + 2);
-        if (ch + 3 < nchunks) { prefetchX(ch + 3); loadA(NSET - 1, ch + 3); }
-      }
       __syncthreads();
     }
   } else if constexpr (K64) {
@@ -267,7 +249,7 @@ __global__ __launch_bounds__(512, 2) void gemm_pwln_kernel(const PwLn q) {
       __syncthreads();
     }
     if (nchunks & 1) sub(nfull, 0, false);          // the odd last 32 channels (its image was staged by chunk nfull - 1's pieces, or by the prologue)
-  } else if constexpr (SSV_PWLN_ROLL) {
+  } else {
     // One register set, re-loaded ROW BLOCK BY ROW BLOCK (round 5): the loop runs row block outermost with all NT input fragments of the chunk
     // in registers, so row block i's weight fragments are dead after its 3 NT MFMAs and chunk c + 1's are requested right there -- every
     // fragment gets (WMB - 1) / WMB of a chunk of lead time.  (Before: the whole set was re-loaded after the chunk's last MFMA, i.e. the first
@@ -300,19 +282,6 @@ __global__ __launch_bounds__(512, 2) void gemm_pwln_kernel(const PwLn q) {
       prefetchXr(min(ch + 2, nchunks - 1));
       __syncthreads();
     }
-  } else {
-    __syncthreads();
-    PW_STAMP(1);
-    for (int ch = 0; ch < nchunks; ++ch) {
-      tap(0, ch);
-      __builtin_amdgcn_sched_barrier(0);            // the re-load stays behind this chunk's MFMAs
-      if (ch + 1 < nchunks) {
-        loadA(0, ch + 1);
-        commitX(ch + 1);
-        if (ch + 2 < nchunks) prefetchX(ch + 2);
-      }
-      __syncthreads();
-    }
   }
 
   // ---- epilogue: pre, LayerNorm over the M rows of every column, activation
@@ -324,7 +293,7 @@ __global__ __launch_bounds__(512, 2) void gemm_pwln_kernel(const PwLn q) {
 #pragma unroll
   for (int t = 0; t < NT; ++t) csum[t] = 0.f;
   // the wave's parked block (rows rbase .. rbase + 15, private to the wave: its LDS operations complete in order) -> dst rows, 16 bytes per lane
-  float* pk = park + (SSV_PWLN_PARK ? wave * 16 * LDWP : 0);
+  float* pk = park + wave * 16 * LDWP;
   auto store_block = [&](float* __restrict__ dst, long row_stride, int rbase) __attribute__((always_inline)) {
 #pragma unroll
     for (int it = 0; it < NT; ++it) {
@@ -379,11 +348,10 @@ __global__ __launch_bounds__(512, 2) void gemm_pwln_kernel(const PwLn q) {
         const float v = rv ? (F16 ? acc[i][t][r] * us : acc[i][t][r]) + add : 0.f;
         acc[i][t][r] = v;
         csum[t] += v;
-        if constexpr (SSV_PWLN_PARK) pk[(kq * 4 + r) * LDWP + t * 16 + nq] = v;
-        else { const int gn = n0 + t * 16 + nq; if (rv && gn < p.N) Cb[(long)gm * p.scm + gn] = v; }
+        pk[(kq * 4 + r) * LDWP + t * 16 + nq] = v;
       }
     }
-    if constexpr (SSV_PWLN_PARK) store_block(Cb, p.scm, (wave * WMB + i) * 16);
+    store_block(Cb, p.scm, (wave * WMB + i) * 16);
   }
   const float invM = 1.f / (float)p.M;
   if constexpr (XR) {                                     // row M - 1: the four k-groups' partial sums of a column, bias; stored, and kept for the LayerNorm
@@ -460,11 +428,10 @@ __global__ __launch_bounds__(512, 2) void gemm_pwln_kernel(const PwLn q) {
         if (q.act == 1) n = fmaxf(n, 0.f);
         else if (q.act == 2) n = 1.f / (1.f + __expf(-n));
         if (rv && gn < p.N) am = fmaxf(am, fabsf(n));
-        if constexpr (SSV_PWLN_PARK) pk[(kq * 4 + r) * LDWP + t * 16 + nq] = n;
-        else if (rv && gn < p.N) Yb[(long)gm * p.N + gn] = n;
+        pk[(kq * 4 + r) * LDWP + t * 16 + nq] = n;
       }
     }
-    if constexpr (SSV_PWLN_PARK) store_block(Yb, p.N, (wave * WMB + i) * 16);
+    store_block(Yb, p.N, (wave * WMB + i) * 16);
   }
   if constexpr (XR) {
     if (tid < BN && n0 + tid < p.N) {                      // row M - 1 of y (colv is final: behind the second reduction's barrier)
@@ -495,7 +462,7 @@ int ssv_launch_gemm_pwln(const GemmNNB& g, const float* gamma, const float* beta
   PwLn q;
   q.g = g; q.gamma = gamma; q.beta = beta; q.y = y; q.ybs = ybs; q.stats = stats; q.y_amax = y_amax; q.namax = namax; q.act = act;
   // M = 513: four row blocks per wave for rows 0 .. 511 and the last row beside the staging (XR) instead of five row blocks
-  const bool xr = SSV_PWLN_XROW && g.xrow_w && g.M == 513 && g.Kpad <= 1056;
+  const bool xr = g.xrow_w && g.M == 513 && g.Kpad <= 1056;
   const int wmb = xr ? 4 : ssv_cdiv(ssv_cdiv(g.M, 16), 8);
   const int nt = 4;
   const dim3 grid(ssv_cdiv(g.N, 16 * nt), g.B);
@@ -792,7 +759,6 @@ __global__ __launch_bounds__(512, 2) void pwln_bwd_kernel(const PwLnBw q) {
 }
 // true when the link's backward can take the one-launch kernel (split-fp16 / split-bf16 planes of the TRANSPOSED weight given; dense dPre)
 bool ssv_pwln_bwd_fused_ok(int B, int Cin, int Cout, int L) {
-  if (!SSV_PWLN_BWD_FUSED) return false;
   // Measured in-step at B = 32 (round 5): links with up to 256 LN rows 24.3 us against 17.9 + 22.6 us in two launches; with 512 / 513 LN rows
   // (one 155 KB workgroup per CU: its three phases cannot overlap with anything) 139 against 74 + 95 us for 513 -> 513 but 139 against 74 + 67 for
   // 512 -> 513 and 123 against ~110 for 256 -> 512: no gain over the step.  Default: the small form only.  SSV_PWLN_BWD=0: never; =2: every shape.

@@ -7,7 +7,6 @@
 #include <stdlib.h>
 #include <string.h>
 #include "ssv_common.h"
-#include "bf3_tuning.h"
 #include <type_traits>
 static_assert(std::is_trivially_copyable<GemmNN>::value && std::is_trivially_copyable<GemmNT>::value && std::is_trivially_copyable<GemmNNB>::value,
               "the GEMM argument structs are kernel arguments");

@@ -326,10 +326,9 @@ __global__ __launch_bounds__(64 * WV, WV == 4 ? 2 : 1) void gemm_nt_bf3_kernel(c
       for (int g = 0; g < G; ++g) {
         if (g + NT_FD < G) frag(g + NT_FD, fb[(g + NT_FD) % (NT_FD + 1)]);
         __builtin_amdgcn_sched_barrier(0);                                   // or the scheduler sinks the reads back to their use
+        // (the k-steps past a ragged row end are multiplied too -- the staged input is zero there: a branch out of the MFMA sequence put an
+        // s_waitcnt vmcnt(0) in the middle of every step's MFMAs, hipcc's wait state being merged at the join)
         const int s2 = g / NTC, q = g % NTC;
-#if !SSV_NT_NOBREAK
-        if (s2 > 0 && q == 0 && ct0[0] + 32 * s2 >= p.La) break;           // ragged last chunk: the k-steps from here on lie past the row end (the input tile is zero there)
-#endif
         const uint4 bh = fb[g % (NT_FD + 1)][0];
         const uint4 bl = fb[g % (NT_FD + 1)][1];
 #pragma unroll
@@ -353,17 +352,13 @@ __global__ __launch_bounds__(64 * WV, WV == 4 ? 2 : 1) void gemm_nt_bf3_kernel(c
         if (((PAR + j) & 1) == 0) commitX(P1{}, ct0[c1], j1); else commitX(P0{}, ct0[c1], j1);
       }
       NT_STAMP(2);
-#if SSV_NT_SPLIT_FIRST
       // the next chunk's dH is split BEFORE the loads of tile s + 2 are issued (round 6): behind them, hipcc's waits for the dH registers came out as
-      // vmcnt(5) .. vmcnt(0) right after those loads, i.e. every step ended by waiting for the tile it had just requested
+      // vmcnt(5) .. vmcnt(0) right after those loads, i.e. every step ended by waiting for the tile it had just requested.  With the k-steps multiplied
+      // past a ragged row end (above) the loop's waits are counted again (tools/isa_loop_waits.py, profiles/round6_nt_bf3_waits.txt): in-step
+      // 118.0 -> 116.8, 28.1 -> 27.7 us -- two workgroups per CU had been covering most of it.
       if (j == KT - 1 && more) splitA(NXT{});
       NT_STAMP(3);
       if (STEADY || s + 2 < steps) loadX(cb[c2], ct0[c2], j2);
-#else
-      if (STEADY || s + 2 < steps) loadX(cb[c2], ct0[c2], j2);
-      NT_STAMP(3);
-      if (j == KT - 1 && more) splitA(NXT{});
-#endif
       NT_STAMP(4);
       __syncthreads();
       NT_STAMP(5);
@@ -463,11 +458,15 @@ int ssv_nt_bf3_tiles(int KT, int M, int Nc) {
   ssv_nt_bf3_tile(KT, M, Nc, &wm, &ntc);
   return ssv_cdiv(ssv_nt_bf3_xrow(KT, M, Nc) ? M - 1 : M, 64 * wm) * ssv_cdiv(Nc, 16 * ntc);
 }
-// the k = 1 weight gradient of 128 j + 1 output rows on the 128 x 96 tile: last row beside the staging, range slabs (gemm_nt_bf3_kernel<.., XR = 1>)
+// the k = 1 weight gradient of 128 j + 1 output rows on the 128 x 96 tile: last row beside the staging, range slabs (gemm_nt_bf3_kernel<.., XR = 1>).
+// The tiles cover rows 0 .. M - 2 and row M - 1 of the product is added by the workgroups of row tile 0 as fp32 dot products of dH(M - 1, t) with the
+// raw input values every staging thread holds before it splits them -- a fifth row tile of MFMAs for ONE row otherwise (30 tiles of 128 x 96 for 24).
+// It pays only together with RANGE slabs (p.bstep == 0: slab z reduces over the z-th of Z equal ranges of the launch's B x tchunks chunks, not over
+// whole batch items): with whole items 24 x 16 workgroups do the same two items each as 30 x 16 did, and the launch lasts as long as its slowest.
 bool ssv_nt_bf3_xrow(int KT, int M, int Nc) {
   int wm, ntc;
   ssv_nt_bf3_tile(KT, M, Nc, &wm, &ntc);
-  return SSV_NT_XROW && KT == 1 && wm == 2 && ntc == 6 && M > 128 && M % 128 == 1;
+  return KT == 1 && wm == 2 && ntc == 6 && M > 128 && M % 128 == 1;
 }
 
 // the kernel addresses both operands with 32-bit element offsets
@@ -493,13 +492,11 @@ int ssv_launch_gemm_nt_bf3(const GemmNT& g, hipStream_t st) {
   SSV_CHECK(!g.f16 || g.jobs || (g.a_amax && g.x_amax && g.a_namax > 0 && g.x_namax > 0), SSV_BAD_SHAPE, "gemm_nt_bf3: split-fp16 needs both operand scales");
   // the ring kernel (k = 3): every shift within one block (64 time steps) either way.  With a job table the shifts are on the device: the caller states their bound.
   int ring_ms = -1;
-#if SSV_NT_RING
   if (g.KT == 3 && wm == 2 && ntc == 4) {
     ring_ms = g.max_shift;
     if (!g.jobs) { ring_ms = 0; for (int j = 0; j < 3; ++j) ring_ms = abs(g.shift[j]) > ring_ms ? abs(g.shift[j]) : ring_ms; }
     if (ring_ms > 64) ring_ms = -1;
   }
-#endif
   if (ssv_shape_log_on()) {
     char nm[96], note[96];
     const int nj = g.jobs ? g.njobs : 1;
@@ -528,8 +525,9 @@ int ssv_launch_gemm_nt_bf3(const GemmNT& g, hipStream_t st) {
     if (g.f16) hipLaunchKernelGGL((gemm_nt_bf3_kernel<K_, A_, C_, 1>), grid, dim3(256), 0, st, g, mtiles); \
     else hipLaunchKernelGGL((gemm_nt_bf3_kernel<K_, A_, C_, 0>), grid, dim3(256), 0, st, g, mtiles); \
     return ssv_check_launch("gemm_nt_bf3"); }
-  SSV_NT(3, 2, 4) SSV_NT(3, 2, 2) SSV_NT(3, 1, 4) SSV_NT(3, 1, 2)
-  SSV_NT(1, 2, 8) SSV_NT(1, 2, 6) SSV_NT(1, 2, 4) SSV_NT(1, 2, 2) SSV_NT(1, 1, 6) SSV_NT(1, 1, 4) SSV_NT(1, 1, 2)
+  // exactly the tiles ssv_nt_bf3_tile can return (SSV_NT_FORCE sets the slab count, not the tile); <3, 2, 4> is the k = 3 form for shifts past the ring's reach
+  SSV_NT(3, 2, 4)
+  SSV_NT(1, 2, 8) SSV_NT(1, 2, 6) SSV_NT(1, 2, 2) SSV_NT(1, 1, 4)
 #undef SSV_NT
   return ssv_fail(SSV_UNSUPPORTED, "gemm_nt_bf3: no tile %d,%d for kernel size %d", wm, ntc, g.KT);
 }

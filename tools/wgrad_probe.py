@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""Diagnostic (GPU box): isolated time of the weight-gradient launch at the hot layer shapes -- for SSV_ABL tuning builds of the
-library (SSV_HIP_LIB=...), whose results are wrong by construction and cannot run inside the training step."""
+"""Diagnostic (GPU box): isolated time of the weight-gradient launch at the hot layer shapes (k = 3 and k = 1), for the tree's library or a
+variant build (tools/build_variant.sh, SSV_HIP_LIB=...) -- also one whose results are wrong and that cannot run inside the training step."""
 import sys, os
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
