@@ -459,6 +459,25 @@ int ssv_sv_eer_sweep(const float* sim, int N, int V, const float* thr, int nthr,
  * rates[m] (float32) = trials of the own-speaker column in the last `tail` rows with sim > thres, / float(tail) / N.  The comparison is
  * float32 against the float32 rounding of the threshold, as the reference's `mat > thres` compares a float32 matrix with a Python float. */
 int ssv_sv_accept_rate(const float* sim_stack, int nmat, int N, int V, int tail, float thres, float* rates, ssv_stream_t stream);
+/* The counting of the GE2E sweep of curve.py:15-25 (5,000 thresholds over a similarity matrix), over a DEVICE stack of nmat matrices
+ * (N, V, N) in ONE launch that reads every matrix once per tile of ssv_sv_curve_tile() thresholds (ssv_sv_eer_sweep reads it once per
+ * threshold).  thr: DEVICE array of nthr float32 thresholds, NON-DECREASING (duplicates allowed; not checked on the device: the caller
+ * checks before the upload).  counts (nmat, nthr, 4) int32 OUT, the four columns of ssv_sv_eer_sweep per matrix: trials with
+ * sim > thr[t] (strict, float32) over the whole matrix, the own-speaker column, its first `head` rows, its last `tail` rows
+ * (head + tail > V is allowed: a row may be in both).  A NaN score is accepted by no threshold, +inf by every finite one, -inf by none.
+ * Every element of counts is written and nothing is added to what it held.  Integer sums in LDS, no global atomics: the same bits on
+ * every run.  nmat, N, V, nthr < 1, head or tail outside [0, V]: -1 before anything is launched; more than 2^31 - 1 trials per matrix
+ * (or more than 65535 matrices): -2. */
+int ssv_sv_score_curve(const float* sim_stack, int nmat, int N, int V, int head, int tail, const float* thr, int nthr, int* counts, ssv_stream_t stream);
+/* The same for a list of n scores with a class code each -- the counting of the i-vector sweep of curve.py:45-49 (real and fake score
+ * arrays against 8,000 thresholds) and of kaldi_ivectors/ivector_spoofrate.py:18-22 (one threshold): counts (nthr, nclass) int32 OUT,
+ * counts[t][c] = items with cls[e] == c and scores[e] > thr[t] (strict, in the scores' own type); 1 <= nclass <= 4, an item whose code
+ * is >= nclass is counted nowhere.  scores, cls, thr on the DEVICE, thr non-decreasing.  _f64 compares float64 scores with float64
+ * thresholds as the reference's numpy arrays do; _f32 serves float32 score vectors.  n < 1, nthr < 1, nclass outside [1, 4]: -1;
+ * n > 2^31 - 1: -2. */
+int ssv_score_list_curve_f32(const float* scores, const unsigned char* cls, long n, int nclass, const float* thr, int nthr, int* counts, ssv_stream_t stream);
+int ssv_score_list_curve_f64(const double* scores, const unsigned char* cls, long n, int nclass, const double* thr, int nthr, int* counts, ssv_stream_t stream);
+int ssv_sv_curve_tile(void);      /* thresholds one workgroup of the three entries above owns (tests put nthr on its edges) */
 
 /* ---- Vocoder and spectrogram front end ------------------------------------------------
  * Replaces the CPU tail of synthesis, synthesize.py:138-147 / generate_test_utterances.py:128-139

@@ -1,6 +1,7 @@
 // The speaker-verification test on the device (GE2E/train_speech_embedder.py:112-322 around the embedder), gfx950: the trial scores of
 // get_centroids + get_cossim (ssv_sv_trial_scores), the threshold sweep that ends in EER and spoof rate (ssv_sv_eer_sweep) and the
-// accept rate at a given threshold over a stack of score matrices (ssv_sv_accept_rate).  Latency-class: 20 x 80 x 20 dot products of
+// accept rate at a given threshold over a stack of score matrices (ssv_sv_accept_rate); and the counting of curve.py's two sweeps and of
+// kaldi_ivectors/ivector_spoofrate.py, thousands of thresholds in one pass (ssv_sv_score_curve, ssv_score_list_curve_*).  Latency-class: 20 x 80 x 20 dot products of
 // 256 and 50 x 32000 comparisons at the configuration's shape -- what counts is that a batch is three launches and no host traffic.
 // Every float sum runs in a fixed order that does not depend on the grid, every count is an integer: the same inputs give the same bits.
 #include "ssv_common.h"
@@ -211,4 +212,130 @@ extern "C" int ssv_sv_accept_rate(const float* sim_stack, int nmat, int N, int V
   SSV_CHECK((long)N * tail <= 0x7fffffffL && (long)N * tail < (1L << 24), SSV_UNSUPPORTED, "sv_accept_rate: %ld trials per matrix are not exact in float32", (long)N * tail);
   hipLaunchKernelGGL(sv_accept_rate_kernel, dim3(nmat), dim3(SE_THREADS), 0, (hipStream_t)stream, sim_stack, N, V, tail, thres, rates);
   return ssv_check_launch("sv_accept_rate");
+}
+
+// ---- spoof-rate / FRR curves: thousands of thresholds in one pass --------------------------------------------------------------------
+// The sweep above gives every threshold a workgroup that reads the whole matrix: right for 50 thresholds, 5,000 passes for curve.py's.
+// Here a workgroup owns a TILE of SC_TILE sorted thresholds, staged in LDS, and walks its matrix (or score list) once.  Per score x:
+// p = the number of tile thresholds strictly below x (a lower-bound search; sorted thresholds make x > thr[t] the same as t < p, with
+// duplicates too; every comparison of a NaN is false, so a NaN gives 0), then an integer atomicAdd on bin p of an LDS histogram of
+// (SC_TILE + 1) bins x 4 classes.  The two ends never reach the LDS: p = 0 (x above no threshold of the tile) adds to no count, and a
+// score above the whole tile -- the common case: a tile spans 0.0256 of curve.py's range -- is counted in registers and the wave's sum
+// goes to the top bin once at the end, so a crowd of scores in one bin costs no serialised atomics.  (Scores crowding ONE bin inside the
+// tile do serialise, 64 lanes on an address at worst: 125 walk steps of 4 atomics at the configuration's shape, microseconds.)  A suffix
+// sum over the bins then gives the tile's rows of counts: a score above the tile is in every row, one below it in none, so tiles need
+// nothing from each other -- no global atomics, no second launch, no arrival order; integer sums: the same bits on every run.
+// SC_TILE = 256 = the workgroup: thread t owns threshold t in the scan and the store.  The LDS is 2 KiB of thresholds (as doubles) and
+// 4 KiB of bins, no limit on occupancy; what the tile sets is the number of passes over the data, ceil(nthr / 256) = 20 for 5,000
+// thresholds, against the workgroups there are to fill the device with (20 per matrix), and the 8 steps of a search.
+#define SC_TILE 256
+
+__device__ __forceinline__ int sc_wave_sum(int v) {
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) v += __shfl_xor(v, o);
+  return v;
+}
+
+// STACK: scores = blockIdx.y-th matrix (N, V, N) of n = N * V * N trials, classes (whole matrix, own column, its first `head` rows, its
+// last `tail` rows), NC = 4 columns of counts.  Otherwise a list of n items with class codes cls[e] (>= NC: counted nowhere), NC columns.
+template <typename T, bool STACK>
+__global__ __launch_bounds__(SC_TILE) void score_curve_kernel(const T* __restrict__ scores, const unsigned char* __restrict__ cls, long n, int N, int V, int head,
+                                                              int tail, int NC, const T* __restrict__ thr, int nthr, int* __restrict__ counts) {
+  __shared__ T th[SC_TILE];
+  __shared__ int4 hist[SC_TILE + 1];
+  const int tid = threadIdx.x, t0 = blockIdx.x * SC_TILE, nt = min(SC_TILE, nthr - t0);
+  if (tid < nt) th[tid] = thr[t0 + tid];
+  hist[tid] = make_int4(0, 0, 0, 0);
+  if (tid == 0) hist[SC_TILE] = make_int4(0, 0, 0, 0);
+  __syncthreads();
+  const T lo_t = th[0], hi_t = th[nt - 1];
+  const T* __restrict__ s = scores + (STACK ? (long)blockIdx.y * n : 0L);
+  int* bins = (int*)hist;
+  int top[4] = {0, 0, 0, 0};
+  for (long e = tid; e < n; e += SC_TILE) {
+    const T x = s[e];
+    if (!(x > lo_t)) continue;                       // above no threshold of the tile (a NaN, -inf): in none of its counts
+    unsigned mask;
+    if (STACK) {
+      const unsigned u = (unsigned)e, r = u / (unsigned)N;
+      const int j = (int)(u - r * (unsigned)N), i = (int)(r / (unsigned)V), v = (int)(r - (unsigned)i * (unsigned)V);
+      const unsigned own = i == j;
+      mask = 1u | own << 1 | (own & (unsigned)(v < head)) << 2 | (own & (unsigned)(v >= V - tail)) << 3;
+    } else {
+      const unsigned c = cls[e];
+      mask = c < (unsigned)NC ? 1u << c : 0u;
+    }
+    if (x > hi_t) {                                  // above the whole tile: the top bin, kept in registers
+#pragma unroll
+      for (int k = 0; k < 4; ++k) top[k] += (int)(mask >> k & 1u);
+      continue;
+    }
+    int lo = 1, hi = nt - 1;                         // th[0] < x and not th[nt - 1] < x: p lies in [1, nt - 1]
+    while (lo < hi) {
+      const int mid = (lo + hi) >> 1;
+      if (th[mid] < x) lo = mid + 1; else hi = mid;
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+      if (mask >> k & 1u) atomicAdd(&bins[lo * 4 + k], 1);
+  }
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const int w = sc_wave_sum(top[k]);
+    if ((tid & 63) == 0 && w) atomicAdd(&bins[nt * 4 + k], w);
+  }
+  __syncthreads();
+  // counts[t] = bins t + 1 ... SC_TILE summed (the bins past nt hold zeros): thread t starts from bin t + 1, eight doubling steps
+  int4 a = hist[tid + 1];
+  for (int d = 1; d < SC_TILE; d <<= 1) {
+    int4 b = make_int4(0, 0, 0, 0);
+    if (tid + d < SC_TILE) b = hist[tid + 1 + d];
+    __syncthreads();
+    a.x += b.x; a.y += b.y; a.z += b.z; a.w += b.w;
+    hist[tid + 1] = a;
+    __syncthreads();
+  }
+  if (tid < nt) {
+    int* out = counts + ((STACK ? (long)blockIdx.y * nthr : 0L) + t0 + tid) * NC;
+    const int r[4] = {a.x, a.y, a.z, a.w};
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+      if (k < NC) out[k] = r[k];
+  }
+}
+
+extern "C" int ssv_sv_curve_tile(void) { return SC_TILE; }
+
+extern "C" int ssv_sv_score_curve(const float* sim_stack, int nmat, int N, int V, int head, int tail, const float* thr, int nthr, int* counts,
+                                  ssv_stream_t stream) {
+  SSV_CHECK(sim_stack && thr && counts, SSV_BAD_SHAPE, "sv_score_curve: null pointer (sim_stack, thr and counts are required)");
+  SSV_CHECK(nmat >= 1 && N >= 1 && V >= 1 && nthr >= 1, SSV_BAD_SHAPE, "sv_score_curve: need nmat >= 1, N >= 1, V >= 1 and nthr >= 1; got nmat=%d N=%d V=%d nthr=%d",
+            nmat, N, V, nthr);
+  SSV_CHECK(head >= 0 && tail >= 0 && head <= V && tail <= V, SSV_BAD_SHAPE, "sv_score_curve: head=%d and tail=%d must lie in [0, V=%d]", head, tail, V);
+  SSV_CHECK((long)N * V * N <= 0x7fffffffL, SSV_UNSUPPORTED, "sv_score_curve: %ld trials per matrix do not fit the int32 counts", (long)N * V * N);
+  SSV_CHECK(nmat <= 65535, SSV_UNSUPPORTED, "sv_score_curve: nmat=%d matrices exceed the grid (65535 per call)", nmat);
+  hipLaunchKernelGGL((score_curve_kernel<float, true>), dim3(ssv_cdiv(nthr, SC_TILE), nmat), dim3(SC_TILE), 0, (hipStream_t)stream, sim_stack,
+                     (const unsigned char*)nullptr, (long)N * V * N, N, V, head, tail, 4, thr, nthr, counts);
+  return ssv_check_launch("sv_score_curve");
+}
+
+template <typename T>
+static int score_list_curve(const char* what, const T* scores, const unsigned char* cls, long n, int nclass, const T* thr, int nthr, int* counts,
+                            ssv_stream_t stream) {
+  SSV_CHECK(scores && cls && thr && counts, SSV_BAD_SHAPE, "%s: null pointer (scores, cls, thr and counts are required)", what);
+  SSV_CHECK(n >= 1 && nthr >= 1 && nclass >= 1 && nclass <= 4, SSV_BAD_SHAPE, "%s: need n >= 1, nthr >= 1 and 1 <= nclass <= 4; got n=%ld nthr=%d nclass=%d", what, n,
+            nthr, nclass);
+  SSV_CHECK(n <= 0x7fffffffL, SSV_UNSUPPORTED, "%s: %ld items do not fit the int32 counts", what, n);
+  hipLaunchKernelGGL((score_curve_kernel<T, false>), dim3(ssv_cdiv(nthr, SC_TILE)), dim3(SC_TILE), 0, (hipStream_t)stream, scores, cls, n, 1, 1, 0, 0, nclass, thr,
+                     nthr, counts);
+  return ssv_check_launch(what);
+}
+
+extern "C" int ssv_score_list_curve_f32(const float* scores, const unsigned char* cls, long n, int nclass, const float* thr, int nthr, int* counts,
+                                        ssv_stream_t stream) {
+  return score_list_curve<float>("score_list_curve_f32", scores, cls, n, nclass, thr, nthr, counts, stream);
+}
+extern "C" int ssv_score_list_curve_f64(const double* scores, const unsigned char* cls, long n, int nclass, const double* thr, int nthr, int* counts,
+                                        ssv_stream_t stream) {
+  return score_list_curve<double>("score_list_curve_f64", scores, cls, n, nclass, thr, nthr, counts, stream);
 }

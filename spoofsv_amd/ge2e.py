@@ -7,7 +7,8 @@ BASELINE.json's north_star asks) and backward (one iteration
 through ``train_iteration``, which ends in torch's own clip_grad_norm_ and SGD; ``GE2ETrainStep``, the iteration on a corpus held
 on the device, runs those too in libssv_hip.so: ``ClipSGD``, and ``tisv_batch_gather`` for the batch).  The verification test around the
 embedder (GE2E/train_speech_embedder.py:112-322: trial scores, threshold sweep, spoof rate) has device operators too -- ``sv_trial_scores``,
-``sv_eer_sweep``, ``sv_accept_rate`` -- and ``SvEvalStep`` runs a batch of it on a resident corpus.  State-dict keys equal the
+``sv_eer_sweep``, ``sv_accept_rate`` -- and ``SvEvalStep`` runs a batch of it on a resident corpus; ``sv_score_curve`` and
+``score_list_curve`` count for the curves of curve.py (thousands of thresholds, one pass over the scores).  State-dict keys equal the
 reference's (``LSTM_stack.weight_ih_l0`` ... ``projection.bias``), so its checkpoints load unchanged.
 
 The reference reads its sizes from a module-global ``hparam`` loaded from config/config.yaml; here they
@@ -559,6 +560,52 @@ def sv_accept_rate(sim_stack, thres, eval_num):
     rates = torch.empty((max(nmat, 1),), dtype=torch.float32, device=sim_stack.device)
     _lib.call("ssv_sv_accept_rate", _p(sim_stack), nmat, N, V, 2 * int(eval_num), float(thres), _p(rates), _stream())
     return [float(r) for r in rates.cpu()]
+
+
+def _curve_thresholds(thresholds, dtype, what):
+    """A host sequence of thresholds -> numpy array in the scores' type.  Checked here, in that type and before anything touches the device,
+    because the kernel does not: non-decreasing (duplicates pass) and no NaN."""
+    t = np.asarray(thresholds, dtype=np.float64).astype(np.float32 if dtype == torch.float32 else np.float64)
+    if t.ndim != 1 or t.size < 1:
+        raise ValueError("%s: need a non-empty one-dimensional sequence of thresholds, got shape %s" % (what, tuple(t.shape)))
+    if np.isnan(t).any() or (t[1:] < t[:-1]).any():
+        raise ValueError("%s: the thresholds must be non-decreasing and free of NaN (the kernel searches them)" % what)
+    return t
+
+
+def sv_score_curve(sim_stack, thresholds, head, tail):
+    """The counts behind curve.py's GE2E sweep for every matrix of a device stack (nmat, N, V, N) and every threshold of the host sequence
+    ``thresholds`` (non-decreasing; compared as their float32 roundings, strictly, as ``sim > thres`` compares a float32 matrix with a Python
+    float), in one launch (``ssv_sv_score_curve``): int32 (nmat, K, 4) on the device -- accepted trials of the whole matrix, the own-speaker
+    column, its first ``head`` rows, its last ``tail`` rows, the columns of ``sv_eer_sweep(return_counts=True)``.  Nothing is read back."""
+    thr = _curve_thresholds(thresholds, torch.float32, "sv_score_curve")
+    _dev(sim_stack, "similarity stack")
+    if sim_stack.dim() != 4 or sim_stack.shape[1] != sim_stack.shape[3] or sim_stack.dtype != torch.float32:
+        raise RuntimeError("sv_score_curve: need a float32 stack (nmat, N, V, N), got %s %s" % (sim_stack.dtype, tuple(sim_stack.shape)))
+    thr, K = torch.from_numpy(thr).to(sim_stack.device), int(thr.size)
+    sim_stack = sim_stack.contiguous()
+    nmat, N, V, _ = sim_stack.shape
+    counts = torch.empty((max(nmat, 1), K, 4), dtype=torch.int32, device=sim_stack.device)
+    _lib.call("ssv_sv_score_curve", _p(sim_stack), nmat, N, V, int(head), int(tail), _p(thr), K, _p(counts), _stream())
+    return counts
+
+
+def score_list_curve(scores, classes, thresholds, nclass):
+    """Per threshold and class the items of a device score vector above the threshold (strict, in the scores' own type): ``scores`` (n,)
+    float32 or float64 -- the dtype picks ``ssv_score_list_curve_f32`` / ``_f64`` --, ``classes`` (n,) uint8 codes (an item whose code is
+    >= ``nclass`` is counted nowhere), ``thresholds`` a non-decreasing host sequence -> int32 (K, nclass) on the device."""
+    thr = _curve_thresholds(thresholds, scores.dtype, "score_list_curve")
+    _dev(scores, "scores")
+    _dev(classes, "classes")
+    if scores.dim() != 1 or scores.dtype not in (torch.float32, torch.float64) or classes.dtype != torch.uint8 or classes.shape != scores.shape:
+        raise RuntimeError("score_list_curve: need float32 or float64 scores (n,) and uint8 classes (n,), got %s %s and %s %s"
+                           % (scores.dtype, tuple(scores.shape), classes.dtype, tuple(classes.shape)))
+    thr, K = torch.from_numpy(thr).to(scores.device), int(thr.size)
+    scores, classes = scores.contiguous(), classes.contiguous()
+    counts = torch.empty((K, max(int(nclass), 1)), dtype=torch.int32, device=scores.device)
+    entry = "ssv_score_list_curve_f32" if scores.dtype == torch.float32 else "ssv_score_list_curve_f64"
+    _lib.call(entry, _p(scores), _p(classes), scores.numel(), int(nclass), _p(thr), K, _p(counts), _stream())
+    return counts
 
 
 class SvEvalStep:

@@ -7,7 +7,8 @@ loading, the enrollment/verification bookkeeping and the threshold sweep are hos
 ``spoof_evaluation`` the in-memory form of ``test`` for features that never touched a disk.  ``ResidentSpeakerCorpus`` holds the
 training corpus on the device and draws the loader's batches as row tables (``train`` with ``cfg["train"]["resident"]``); with
 ``cfg["test"]["resident"]`` the tests run on a resident test corpus too, scores and sweep in libssv_hip.so (``ge2e.SvEvalStep``), and ``evaluate``
-is the three of them -- ``test``, ``test_nospoof``, ``spoof_rate_at`` -- in one pass.
+is the three of them -- ``test``, ``test_nospoof``, ``spoof_rate_at`` -- in one pass.  ``spoof_curve``, ``ivector_curve``, ``ivector_spoofrate`` and
+``curve`` are the arithmetic of ``curve.py`` and ``kaldi_ivectors/ivector_spoofrate.py`` (spoof rate against the FRR of real speech), counted on the device.
 
 Configuration is a plain dict with the fields of ``GE2E/config/config.yaml`` (``default_config()``), instead of the
 reference's module-global ``hparam`` object.
@@ -20,8 +21,8 @@ import numpy as np
 import torch
 from torch.utils.data import DataLoader, Dataset
 
-from .ge2e import (GE2ELoss, GE2ETrainStep, SpeechEmbedder, SvEvalStep, sv_accept_rate, sv_eer_sweep, sv_eval_shapes, sv_trial_scores, tisv_batch_gather,
-                   train_iteration)
+from .ge2e import (GE2ELoss, GE2ETrainStep, SpeechEmbedder, SvEvalStep, score_list_curve, sv_accept_rate, sv_eer_sweep, sv_eval_shapes, sv_score_curve,
+                   sv_trial_scores, tisv_batch_gather, train_iteration)
 from .ops import require_free_bytes
 
 
@@ -410,12 +411,13 @@ def _test_nospoof_resident(cfg, model_path, enroll_num, eval_num):
 
 
 @torch.no_grad()
-def evaluate(cfg, model_path, enroll_num, eval_num):
+def evaluate(cfg, model_path, enroll_num, eval_num, curve=False):
     """The whole ``__main__`` of train_speech_embedder.py:309-322 -- ``test``, ``test_nospoof``, then the spoof rate at the averaged
     no-spoof threshold -- in ONE pass over a corpus held on the device: every epoch's batches are drawn once, the mixture sweep and the
     no-spoof sweep run on the same embeddings (``SvEvalStep`` with ``eval_num``), and the spoof rate at the threshold comes from the
     mixture matrices the step holds (``sv_accept_rate``).  Two read-backs in all (the sweeps' history, the accept rates), no disk.
-    Returns dict(EER, spoof_rate_at_eer, threshold, spoof_rate), each averaged as the three functions average.
+    Returns dict(EER, spoof_rate_at_eer, threshold, spoof_rate), each averaged as the three functions average.  ``curve=True`` adds
+    ``"curve"``: the ``spoof_curve`` of the matrices the step holds (one more read-back: the curve's counts).
 
     NOT draw for draw the reference's two-pass sequence: there ``test_nospoof`` draws batches of its own after ``test`` has drawn its, so
     its threshold is measured on other speakers' draws than the matrices it is applied to.  Here both sweeps see the same batches; the
@@ -431,8 +433,11 @@ def evaluate(cfg, model_path, enroll_num, eval_num):
         return sum(sum(get(r) for r in ep) / len(ep) for ep in by_epoch) / n
     threshold = avg(lambda r: r["nospoof"]["thres"])
     evaluate.last_step = step
-    return dict(EER=avg(lambda r: r["EER"]), spoof_rate_at_eer=spoof_rate_at(cfg, threshold, eval_num, sims=step.sims()), threshold=threshold,
-                spoof_rate=avg(lambda r: r["spoof_rate"]))
+    out = dict(EER=avg(lambda r: r["EER"]), spoof_rate_at_eer=spoof_rate_at(cfg, threshold, eval_num, sims=step.sims()), threshold=threshold,
+               spoof_rate=avg(lambda r: r["spoof_rate"]))
+    if curve:
+        out["curve"] = spoof_curve(cfg, eval_num, sims=step.sims())
+    return out
 
 
 @torch.no_grad()
@@ -495,6 +500,156 @@ def spoof_rate_at(cfg, thres, eval_num, sims=None):
         idx = torch.arange(N)
         rates.append(float(mat[idx, -2 * eval_num:, idx].float().sum() / float(2 * eval_num) / N))
     return sum(rates) / len(rates)
+
+
+# --------------------------------------------------------------------------------------------- curve.py: spoof rate against real-speech FRR
+def curve_thresholds(kind):
+    """The two threshold lists of curve.py as Python floats: "ge2e" (:15, 5,000 over a similarity matrix), "ivector" (:31, 8,000 over a
+    Kaldi score file)."""
+    if kind == "ge2e":
+        return [0.0001 * i + 0.5 for i in range(5000)]
+    if kind == "ivector":
+        return [-50 + 0.01 * i for i in range(8000)]
+    raise ValueError("curve_thresholds: kind is 'ge2e' or 'ivector', got %r" % (kind,))
+
+
+def ge2e_curve_rates(head_count, tail_count, N, rows):
+    """curve.py:21-22 from the counts of accepted own-speaker trials in the first / last ``rows`` verification rows: the script sums float32
+    tensors that hold integers (exact), divides twice in float32 and ``.item()`` widens the result --
+    spoof_rate = float32(tail) / float32(rows) / float32(N), gt_frr = (float32(N * rows) - float32(head)) / float32(rows) / float32(N).
+    Returns (spoof_rate, gt_frr) as float64 arrays of the counts' shape."""
+    f = np.float32
+    head, tail = np.asarray(head_count).astype(f), np.asarray(tail_count).astype(f)
+    spoof = tail / f(rows) / f(N)
+    frr = (f(N * rows) - head) / f(rows) / f(N)
+    return spoof.astype(np.float64), frr.astype(np.float64)
+
+
+def _load_simmat(simmat):
+    if isinstance(simmat, (str, os.PathLike)):
+        path = os.fspath(simmat)
+        simmat = np.load(path) if path.endswith(".npy") else torch.load(path, map_location="cpu")
+    return torch.as_tensor(simmat)
+
+
+def spoof_curve(cfg, eval_num=20, sims=None, simmat=None, thresholds=None):
+    """The GE2E half of curve.py (:15-25) -- per threshold the spoof rate (accepted own-speaker trials of the last 2*eval_num verification
+    rows) and the FRR of real speech (rejected ones of the first 2*eval_num) -- over a device stack ``sims`` (nmat, N, V, N)
+    (``SvEvalStep.sims()``) or over one saved matrix ``simmat`` as the script reads it (a ``torch.save``d tensor; also a .npy file or a
+    tensor), of cfg["test"]["N"] speakers.  ``thresholds``: default ``curve_thresholds("ge2e")``.  The counting is one launch
+    (``ge2e.sv_score_curve``) and one read-back, the counts.  Returns dict(thresholds, spoof_rate, gt_frr, counts, pooled): the two rates
+    per matrix, (nmat, K) float64, bit for bit the script's logs (its float32 rounding sequence, ``ge2e_curve_rates``); counts (nmat, K, 4)
+    int32 on the host; and ``pooled`` = dict(spoof_rate, gt_frr), (K,) float64: the same two rates from the counts SUMMED over the stack and
+    divided in float64.  ``pooled`` is this project's, not the reference's, which draws one matrix."""
+    if (sims is None) == (simmat is None):
+        raise ValueError("spoof_curve: give either sims (a device stack) or simmat (one saved matrix)")
+    thresholds = curve_thresholds("ge2e") if thresholds is None else [float(t) for t in thresholds]
+    if sims is None:
+        m = _load_simmat(simmat)
+        if m.dim() != 3 or m.shape[0] != m.shape[2] or m.shape[0] != int(cfg["test"]["N"]):
+            raise ValueError("spoof_curve: the matrix is %s, expected (N, V, N) with N = cfg['test']['N'] = %d" % (tuple(m.shape), int(cfg["test"]["N"])))
+        sims = m.float().unsqueeze(0).to(torch.device(cfg["device"]))
+    if sims.dim() != 4:
+        raise ValueError("spoof_curve: sims is %s, expected a stack (nmat, N, V, N)" % (tuple(sims.shape),))
+    nmat, N, V, rows = sims.shape[0], sims.shape[1], sims.shape[2], 2 * int(eval_num)
+    if not 1 <= rows <= V:
+        raise ValueError("spoof_curve: 2 * eval_num = %d must lie in [1, V = %d]" % (rows, V))
+    counts = sv_score_curve(sims, thresholds, rows, rows).cpu().numpy()
+    spoof, frr = ge2e_curve_rates(counts[:, :, 2], counts[:, :, 3], N, rows)
+    total = float(nmat * N * rows)
+    head, tail = counts[:, :, 2].astype(np.int64).sum(axis=0), counts[:, :, 3].astype(np.int64).sum(axis=0)
+    pooled = dict(spoof_rate=tail.astype(np.float64) / total, gt_frr=(total - head.astype(np.float64)) / total)
+    return dict(thresholds=thresholds, spoof_rate=spoof, gt_frr=frr, counts=counts, pooled=pooled)
+
+
+def parse_ivector_scores(score_file, enroll_utt_num=3, eval_utt_num=20):
+    """curve.py:32-41's reading of a Kaldi trial-score file (`<model speaker> <utterance> <score>` per line): a trial counts only when
+    the utterance is the model speaker's own (info[0] == info[1][:3]); its utterance number (the name's last three characters) above
+    enroll + eval makes it a spoofing trial, otherwise a real one.  Returns (real, fake) float64 arrays, in file order."""
+    real, fake = [], []
+    with open(score_file, "r") as f:
+        for content in f.readlines():
+            info = content.strip().split()
+            if not info or info[0] != info[1][:3]:
+                continue
+            (fake if int(info[1][-3:]) > enroll_utt_num + eval_utt_num else real).append(float(info[-1]))
+    return np.array(real, dtype=np.float64), np.array(fake, dtype=np.float64)
+
+
+def _list_counts(device, groups, thresholds):
+    """counts (K, len(groups)) on the host: per threshold the scores of each group above it, in float64 on the device."""
+    scores = np.concatenate(groups)
+    cls = np.concatenate([np.full(len(g), c, dtype=np.uint8) for c, g in enumerate(groups)])
+    dev = torch.device(device)
+    return score_list_curve(torch.from_numpy(scores).to(dev), torch.from_numpy(cls).to(dev), thresholds, len(groups)).cpu().numpy()
+
+
+def ivector_curve(score_file, enroll_utt_num=3, eval_utt_num=20, thresholds=None, device="cuda"):
+    """The i-vector half of curve.py (:27-49): the file parsed on the host (``parse_ivector_scores``), the 8,000 thresholds
+    (``curve_thresholds("ivector")`` unless given) counted on the device in float64 (``ge2e.score_list_curve``), then
+    spoof_rate = fake_count / L and gt_frr = 1 - real_count / L in float64, as the script computes them.  Unequal numbers of real and
+    spoofing trials are a ``ValueError`` (the script asserts).  Returns dict(thresholds, spoof_rate, gt_frr, counts (K, 2): real, fake)."""
+    real, fake = parse_ivector_scores(score_file, enroll_utt_num, eval_utt_num)
+    if len(real) != len(fake) or len(real) == 0:
+        raise ValueError("ivector_curve: %s holds %d real and %d spoofing own-speaker trials; curve.py:42 needs as many of one as of the other (and some)"
+                         % (score_file, len(real), len(fake)))
+    thresholds = curve_thresholds("ivector") if thresholds is None else [float(t) for t in thresholds]
+    counts = _list_counts(device, [real, fake], thresholds)
+    L = len(real)
+    return dict(thresholds=thresholds, spoof_rate=counts[:, 1].astype(np.int64) / L, gt_frr=1 - counts[:, 0].astype(np.int64) / L, counts=counts)
+
+
+def ivector_spoofrate(score_file, thres, train_spk_num=88, enroll_utt_num=3, eval_utt_num=20, device="cuda"):
+    """kaldi_ivectors/ivector_spoofrate.py whole: the spoofing own-speaker trials of a score file accepted at ``thres`` (score > thres in
+    float64; counted by the list entry with one threshold), over total_num = (lines / 2) // (108 - train_spk_num), which must equal
+    (108 - train_spk_num) * eval_utt_num (the script asserts; a ``ValueError`` here)."""
+    with open(score_file, "r") as f:
+        lines = f.readlines()
+    total_num = (len(lines) / 2) // (108 - train_spk_num)
+    if total_num != (108 - train_spk_num) * eval_utt_num:
+        raise ValueError("ivector_spoofrate: %d lines give total_num = %s, expected (108 - %d) * %d = %d (ivector_spoofrate.py:16)"
+                         % (len(lines), total_num, train_spk_num, eval_utt_num, (108 - train_spk_num) * eval_utt_num))
+    spoof = []
+    for line in lines:
+        score = line.strip().split()
+        if score[0] == score[1][:3] and int(score[1][-3:]) > enroll_utt_num + eval_utt_num:
+            spoof.append(float(score[2]))
+    if not spoof:
+        return 0 / total_num
+    counts = _list_counts(device, [np.array(spoof, dtype=np.float64)], [float(thres)])
+    return int(counts[0, 0]) / total_num
+
+
+def curve(cfg, simmat, ivector_score=None, out_dir=".", eval_num=20, plot=None):
+    """curve.py: both sweeps, written to ``out_dir``/curve.npz under the script's four names (spoof_rate_log, gt_frr_log for the GE2E matrix;
+    spoof_rate_log_2, gt_frr_log_2 for the i-vector score file, empty without one) with the two threshold lists (thresholds, thresholds_2).
+    The figure ``out_dir``/curve.png is drawn only when matplotlib imports and ``plot`` is not False; nothing else needs matplotlib.
+    Returns the dict that was saved."""
+    ge = spoof_curve(cfg, eval_num, simmat=simmat)
+    out = dict(spoof_rate_log=ge["spoof_rate"][0], gt_frr_log=ge["gt_frr"][0], thresholds=np.array(ge["thresholds"]),
+               spoof_rate_log_2=np.zeros(0), gt_frr_log_2=np.zeros(0), thresholds_2=np.array(curve_thresholds("ivector")))
+    if ivector_score is not None:
+        iv = ivector_curve(ivector_score, device=cfg["device"])
+        out.update(spoof_rate_log_2=iv["spoof_rate"], gt_frr_log_2=iv["gt_frr"])
+    os.makedirs(out_dir, exist_ok=True)
+    np.savez(os.path.join(out_dir, "curve.npz"), **out)
+    if plot is not False:
+        try:
+            import matplotlib
+            matplotlib.use("Agg")
+            import matplotlib.pyplot as plt
+        except ImportError:
+            plt = None
+        if plt is not None:
+            fig = plt.figure()
+            ax = fig.add_subplot(111)
+            for tag, style, label in (("", "r--", "GE2E"), ("_2", "b", "i-vectors")):
+                ax.plot(out["spoof_rate_log" + tag], out["gt_frr_log" + tag], style, linewidth=1, label=label)
+            ax.set(xlabel="Spoof Rate", ylabel="FRR in real speech")
+            ax.legend()
+            fig.savefig(os.path.join(out_dir, "curve.png"))
+            plt.close(fig)
+    return out
 
 
 def read_wav(path):
