@@ -479,6 +479,55 @@ int ssv_score_list_curve_f32(const float* scores, const unsigned char* cls, long
 int ssv_score_list_curve_f64(const double* scores, const unsigned char* cls, long n, int nclass, const double* thr, int nthr, int* counts, ssv_stream_t stream);
 int ssv_sv_curve_tile(void);      /* thresholds one workgroup of the three entries above owns (tests put nthr on its edges) */
 
+/* ---- I-vector groundwork: cepstral features, diagonal UBM, Baum-Welch statistics (additions; ABI version unchanged) ----
+ * The bottom of the reference's kaldi_ivectors/run.sh (MFCC -> VAD -> diagonal UBM -> ...), as far as the diagonal UBM and the
+ * per-utterance statistics.  Kaldi's binaries are NOT reproduced (its MFCC window, snip-edges, energy, VAD and the recipe's conf/ values
+ * are unknown here); the algorithms are the ones stated below.  All arithmetic is independent of ssv_set_precision: the two products run
+ * on v_mfma_f32_16x16x4_f32 (exact fp32 fma chains).  No float atomics, the same inputs give the same bits; nothing is read on the host
+ * except where an argument is said to be a HOST array.  Bad arguments: -1; a shape beyond a kernel's tiles: -2; both before any launch.
+ *
+ * Features.  mel (G, M): the compact frames-major log-mel array of the d-vector path; utt_off (U + 1) int64 DEVICE, ascending: frames
+ * [utt_off[u], utt_off[u+1]) are utterance u (T frames; T = 0 writes nothing; frames in no utterance are not written).  dct (Cc, M) or
+ * NULL (then the statics are mel itself and Cc must equal M).  out (G, Cc * (delta_order + 1)), rows [s, d, dd]:
+ *   s_t = dct . mel_t;   d_t = sum_{j=-w..w} c_j s_{clamp(t+j)},  c_j = j / (2 sum_{i=1..w} i^2);   dd_t = sum_{j=-2w..2w} (c (*) c)_j s_{clamp(t+j)},
+ *   clamp to [0, T-1] (the order of sid/train_diag_ubm.sh: add-deltas, then sliding CMN);  then on ALL columns the centred sliding mean over
+ *   W = cmn_window frames: lo = t - W/2, hi = lo + W; lo < 0: lo = 0, hi = min(T, W); hi > T: hi = T, lo = max(0, T - W);
+ *   out_t = v_t - mean(v[lo:hi]), no variance normalisation.  The window sum is slid in double (never a float32 prefix sum).
+ * ws: ssv_ivec_features_workspace bytes (the rows before the mean subtraction).  Cc <= 128, delta_window <= 8, else -2. */
+long ssv_ivec_features_workspace(long G, int Cc, int delta_order);      /* bytes (a long, like its G; 0 for arguments the entry refuses) */
+int ssv_ivec_features(const float* mel, const long* utt_off, const float* dct, float* out, long G, int M, int U, int Cc, int delta_window,
+                      int delta_order, int cmn_window, void* ws, size_t ws_bytes, ssv_stream_t stream);
+/* Gaussian selection and posteriors of a diagonal-covariance GMM.  X (F, D); planes A = mu / var (C, D), B = -1/2 / var (C, D),
+ * g (C) = log w_c - 1/2 sum_d (log 2 pi var_cd + mu_cd^2 / var_cd), float32 (ssv_gmm_diag_update / ssv_gmm_diag_planes write them; with
+ * D % 4 == 0 the planes must be 16-byte aligned).  L_fc = sum_d A_cd x_fd + sum_d B_cd x_fd^2 + g_c, one (F x 2D)(2D x C) product whose
+ * tile of ssv_gmm_frame_tile(D, C) frames x ALL C columns stays in LDS.  Per frame: the nsel largest L, by descending L and, among equal
+ * values, ascending index -> idx (F, nsel) int32; loglik (F) = log-sum-exp over the selected; post (F, nsel) = the soft max over the
+ * selected, entries below min_post set to 0 and the rest renormalised to sum 1 (min_post = 0: no pruning; the largest is never pruned).
+ * The dense (F, C) posterior matrix is never written.  Range: 1 <= D <= 128, nsel <= C <= 2048, nsel <= 32, any F >= 1; beyond: -2. */
+int ssv_gmm_frame_tile(int D, int C);      /* host-only query: frames one workgroup of ssv_gmm_diag_gselect owns (tests put F on its edges) */
+int ssv_gmm_diag_gselect(const float* X, const float* A, const float* B, const float* g, int* idx, float* post, float* loglik, long F, int D, int C,
+                         int nsel, float min_post, ssv_stream_t stream);
+/* Sufficient statistics per segment: slab (S, C, 1 + order * D) float32, slab[s][c] = sum over f in [seg_off[s], seg_off[s+1]) of
+ * gamma_fc [1, x_f, x_f^2] (order = 1: [1, x_f]), gamma given sparsely by idx / post (F, nsel) as ssv_gmm_diag_gselect writes them: the
+ * product Gamma^T [1, X, X^2] with K = frames, a workgroup per (segment, 64 Gaussians).  seg_off (S + 1) int64 DEVICE.  seg_off_host: the
+ * same table as a HOST array, or NULL: when given it is checked here -- ascending, inside [0, F], else -1; the device clamps what it reads
+ * to [0, F] and takes a descending pair as empty, so nothing is followed out of bounds either way.  A segment of length 0 gives exact
+ * zeros; an idx outside [0, C) is skipped; a repeated idx in a row adds.  Segments = utterances, order 1: the Baum-Welch statistics
+ * (N_u, F_u); segments = runs of <= 2048 frames, order 2: the partial sums of an EM pass.  A sum is fp32 chains over 64 frames each, added
+ * in double along the segment and rounded once to float32.
+ * ssv_gmm_stats_reduce: out (n) float64 = sum over s of slab (S, n), added in ascending s, in double. */
+int ssv_gmm_diag_stats(const float* X, const int* idx, const float* post, const long* seg_off, const long* seg_off_host, float* slab, long F, int D,
+                       int C, int nsel, int S, int order, ssv_stream_t stream);
+int ssv_gmm_stats_reduce(const float* slab, double* out, int S, long n, ssv_stream_t stream);
+/* M-step, one launch, all in float64.  stats (C, 1 + 2 D) float64 = (N_c, F_c, S_c); w (C) OUT, mu, var (C, D) IN / OUT:
+ *   w_c = N_c / sum N;  mu = F / N;  var = max(S / N - mu^2, var_floor);  a Gaussian with N_c < min_count (or N_c <= 0) keeps its mu and var
+ *   and takes weight max(w_c, min_weight); then the weights are renormalised to sum 1.  (This rule is the project's own: Kaldi removes or
+ *   splits such a Gaussian.)  A, B (C, D) and g (C) float32 OUT: the planes of the new parameters, each rounded once from double.
+ * ssv_gmm_diag_planes: the planes alone, of given w, mu, var.  C <= 2048, D <= 128, else -2. */
+int ssv_gmm_diag_update(const double* stats, double* w, double* mu, double* var, float* A, float* B, float* g, int C, int D, double var_floor,
+                        double min_count, double min_weight, ssv_stream_t stream);
+int ssv_gmm_diag_planes(const double* w, const double* mu, const double* var, float* A, float* B, float* g, int C, int D, ssv_stream_t stream);
+
 /* ---- Vocoder and spectrogram front end ------------------------------------------------
  * Replaces the CPU tail of synthesis, synthesize.py:138-147 / generate_test_utterances.py:128-139
  * (`librosa.core.griffinlim(S, n_iter=64, hop_length, win_length)`, `signal.lfilter([1], [1, -PREEMPH], y)`, peak

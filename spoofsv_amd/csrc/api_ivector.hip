@@ -1,0 +1,93 @@
+// C-ABI entries of the i-vector front half (include/ssv_hip.h, "I-vector groundwork"): the argument checks, which come before any launch
+// and need no device; the kernels and their tile limits are in ivector.hip.
+#include "ssv_host.h"
+
+#pragma GCC visibility push(hidden)      // defined in ivector.hip
+int ivec_launch_features(const float* mel, const long* utt_off, const float* dct, float* out, float* v, long G, int M, int U, int Cc, int order, int w, int W,
+                         hipStream_t st);
+int ivec_gselect_tile(int D, int C, size_t* lds_bytes);
+int ivec_launch_gselect(const float* X, const float* A, const float* B, const float* g, int* idx, float* post, float* loglik, long F, int D, int C, int nsel,
+                        float min_post, hipStream_t st);
+int ivec_launch_stats(const float* X, const int* idx, const float* post, const long* seg_off, float* slab, long F, int D, int C, int nsel, int S, int order,
+                      hipStream_t st);
+int ivec_launch_reduce(const float* slab, double* out, int S, long n, hipStream_t st);
+int ivec_launch_update(const double* stats, const double* w_in, double* w_out, double* mu, double* var, float* A, float* B, float* g, int C, int D,
+                       double var_floor, double min_count, double min_weight, hipStream_t st);
+#pragma GCC visibility pop
+
+extern "C" long ssv_ivec_features_workspace(long G, int Cc, int delta_order) {
+  if (G < 1 || Cc < 1 || delta_order < 0 || delta_order > 2) return 0;
+  return (long)align256((size_t)G * Cc * (delta_order + 1) * sizeof(float));
+}
+
+extern "C" int ssv_ivec_features(const float* mel, const long* utt_off, const float* dct, float* out, long G, int M, int U, int Cc, int delta_window,
+                                 int delta_order, int cmn_window, void* ws, size_t ws_bytes, ssv_stream_t stream) {
+  SSV_CHECK(mel && utt_off && out && ws, SSV_BAD_SHAPE, "ivec_features: null pointer (mel, utt_off, out and ws are required)");
+  SSV_CHECK(G >= 1 && M >= 1 && U >= 1 && Cc >= 1 && cmn_window >= 1, SSV_BAD_SHAPE, "ivec_features: need G >= 1, M >= 1, U >= 1, Cc >= 1 and cmn_window >= 1; got G=%ld M=%d U=%d Cc=%d cmn_window=%d",
+            G, M, U, Cc, cmn_window);
+  SSV_CHECK(delta_order >= 0 && delta_order <= 2 && (delta_order == 0 || delta_window >= 1), SSV_BAD_SHAPE,
+            "ivec_features: delta_order=%d must be 0, 1 or 2 and delta_window=%d >= 1 when deltas are asked for", delta_order, delta_window);
+  SSV_CHECK(dct || Cc == M, SSV_BAD_SHAPE, "ivec_features: without a dct table the statics are the mel frames themselves: Cc=%d must equal M=%d", Cc, M);
+  SSV_CHECK(ws_bytes >= (size_t)ssv_ivec_features_workspace(G, Cc, delta_order), SSV_BAD_SHAPE, "ivec_features: workspace of %zu bytes, %ld needed", ws_bytes,
+            ssv_ivec_features_workspace(G, Cc, delta_order));
+  return ivec_launch_features(mel, utt_off, dct, out, (float*)ws, G, M, U, Cc, delta_order, delta_window, cmn_window, (hipStream_t)stream);
+}
+
+extern "C" int ssv_gmm_frame_tile(int D, int C) {
+  SSV_CHECK(D >= 1 && C >= 1, SSV_BAD_SHAPE, "gmm_frame_tile: need D >= 1 and C >= 1; got D=%d C=%d", D, C);
+  const int tf = ivec_gselect_tile(D, C, nullptr);
+  SSV_CHECK(tf > 0, SSV_UNSUPPORTED, "gmm_frame_tile: D=%d, C=%d are beyond the tiles", D, C);
+  return tf;
+}
+
+extern "C" int ssv_gmm_diag_gselect(const float* X, const float* A, const float* B, const float* g, int* idx, float* post, float* loglik, long F, int D, int C,
+                                    int nsel, float min_post, ssv_stream_t stream) {
+  SSV_CHECK(X && A && B && g && idx && post && loglik, SSV_BAD_SHAPE, "gmm_diag_gselect: null pointer (X, A, B, g, idx, post and loglik are required)");
+  SSV_CHECK(F >= 1 && D >= 1 && C >= 1 && nsel >= 1 && nsel <= C, SSV_BAD_SHAPE, "gmm_diag_gselect: need F >= 1, D >= 1 and 1 <= nsel <= C; got F=%ld D=%d C=%d nsel=%d", F,
+            D, C, nsel);
+  SSV_CHECK(min_post >= 0.f && min_post < 1.f, SSV_BAD_SHAPE, "gmm_diag_gselect: min_post=%g must lie in [0, 1)", (double)min_post);
+  SSV_CHECK((D & 3) != 0 || (((uintptr_t)A | (uintptr_t)B) & 15) == 0, SSV_BAD_SHAPE, "gmm_diag_gselect: with D %% 4 == 0 the planes A and B must be 16-byte aligned");
+  return ivec_launch_gselect(X, A, B, g, idx, post, loglik, F, D, C, nsel, min_post, (hipStream_t)stream);
+}
+
+extern "C" int ssv_gmm_diag_stats(const float* X, const int* idx, const float* post, const long* seg_off, const long* seg_off_host, float* slab, long F, int D,
+                                  int C, int nsel, int S, int order, ssv_stream_t stream) {
+  SSV_CHECK(X && idx && post && seg_off && slab, SSV_BAD_SHAPE, "gmm_diag_stats: null pointer (X, idx, post, seg_off and slab are required)");
+  SSV_CHECK(F >= 1 && D >= 1 && C >= 1 && nsel >= 1 && nsel <= C && S >= 1, SSV_BAD_SHAPE,
+            "gmm_diag_stats: need F >= 1, D >= 1, 1 <= nsel <= C and S >= 1; got F=%ld D=%d C=%d nsel=%d S=%d", F, D, C, nsel, S);
+  SSV_CHECK(order == 1 || order == 2, SSV_BAD_SHAPE, "gmm_diag_stats: order=%d must be 1 or 2", order);
+  if (seg_off_host) {
+    SSV_CHECK(seg_off_host[0] >= 0 && seg_off_host[S] <= F, SSV_BAD_SHAPE, "gmm_diag_stats: segments [%ld, %ld) leave the %ld frames", seg_off_host[0], seg_off_host[S], F);
+    for (int s = 0; s < S; ++s)
+      SSV_CHECK(seg_off_host[s] <= seg_off_host[s + 1], SSV_BAD_SHAPE, "gmm_diag_stats: seg_off descends at segment %d (%ld > %ld)", s, seg_off_host[s], seg_off_host[s + 1]);
+  }
+  return ivec_launch_stats(X, idx, post, seg_off, slab, F, D, C, nsel, S, order, (hipStream_t)stream);
+}
+
+extern "C" int ssv_gmm_stats_reduce(const float* slab, double* out, int S, long n, ssv_stream_t stream) {
+  SSV_CHECK(slab && out, SSV_BAD_SHAPE, "gmm_stats_reduce: null pointer (slab and out are required)");
+  SSV_CHECK(S >= 1 && n >= 1, SSV_BAD_SHAPE, "gmm_stats_reduce: need S >= 1 and n >= 1; got S=%d n=%ld", S, n);
+  SSV_CHECK((n + 255) / 256 <= 0x7fffffffL, SSV_UNSUPPORTED, "gmm_stats_reduce: n=%ld exceeds the grid", n);
+  return ivec_launch_reduce(slab, out, S, n, (hipStream_t)stream);
+}
+
+static int gmm_cd_ok(const char* what, int C, int D) {
+  SSV_CHECK(C >= 1 && D >= 1, SSV_BAD_SHAPE, "%s: need C >= 1 and D >= 1; got C=%d D=%d", what, C, D);
+  SSV_CHECK(C <= 2048 && D <= 128, SSV_UNSUPPORTED, "%s: C=%d (at most 2048) or D=%d (at most 128) beyond what the other entries take", what, C, D);
+  return 0;
+}
+
+extern "C" int ssv_gmm_diag_update(const double* stats, double* w, double* mu, double* var, float* A, float* B, float* g, int C, int D, double var_floor,
+                                   double min_count, double min_weight, ssv_stream_t stream) {
+  SSV_CHECK(stats && w && mu && var && A && B && g, SSV_BAD_SHAPE, "gmm_diag_update: null pointer (stats, w, mu, var, A, B and g are required)");
+  SSV_TRY(gmm_cd_ok("gmm_diag_update", C, D));
+  SSV_CHECK(var_floor > 0.0 && min_weight > 0.0 && min_weight < 1.0 && min_count >= 0.0, SSV_BAD_SHAPE,
+            "gmm_diag_update: need var_floor > 0, min_count >= 0 and 0 < min_weight < 1; got %g, %g, %g", var_floor, min_count, min_weight);
+  return ivec_launch_update(stats, nullptr, w, mu, var, A, B, g, C, D, var_floor, min_count, min_weight, (hipStream_t)stream);
+}
+
+extern "C" int ssv_gmm_diag_planes(const double* w, const double* mu, const double* var, float* A, float* B, float* g, int C, int D, ssv_stream_t stream) {
+  SSV_CHECK(w && mu && var && A && B && g, SSV_BAD_SHAPE, "gmm_diag_planes: null pointer (w, mu, var, A, B and g are required)");
+  SSV_TRY(gmm_cd_ok("gmm_diag_planes", C, D));
+  return ivec_launch_update(nullptr, w, nullptr, (double*)mu, (double*)var, A, B, g, C, D, 1.0, 0.0, 0.5, (hipStream_t)stream);
+}
