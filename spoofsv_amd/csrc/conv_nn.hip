@@ -1041,6 +1041,10 @@ static int pick_nnb(const GemmNNB& g, hipStream_t st, int smin, int span) {
   //  shape inside the step with SSV_NNB_FORCE, tools/sweep_force.sh: every one of ten shapes +0.03..+0.2 ms; instantiations removed)
   int wm = 2, nt = 7;
   bool forced = false;
+  // column statistics are written per 64-row group of a row tile (m0 / 64 + group): the second group of a 128-row tile that starts at the last 64
+  // rows (M % 128 == 64) does not exist, and its slot is the first group of the NEXT batch item -- past the buffer for the last one.  Such a
+  // product takes 64-row tiles, whatever the cost model or a force says (no model layer is one: the highway layers ask for M = 2 C, C % 64 == 0)
+  const int a_max = (g.colstats && g.M % 128 != 0) ? 1 : 2;
   // LSTM wavefront with two or more layers in one launch (the steady state of the GE2E embedder: 2 x 3072 x 880 x 1536): the
   // cost model below picks 64 x 112 tiles; measured over the 122 steps of config 5, 128 x 64 tiles are 6 % faster
   // (13.8 -> 13.0 ms; 128 x 96: 13.5, 128 x 112: 14.2, 64 x 96: 14.8) as long as they still give every CU two workgroups.
@@ -1079,7 +1083,7 @@ static int pick_nnb(const GemmNNB& g, hipStream_t st, int smin, int span) {
       snprintf(key, sizeof key, "%d:%d:%d=", KT, g.M, g.N);
       const char* hit = strstr(e, key);
       int a = 0, c = 0;
-      if (hit && (hit == e || hit[-1] == ';') && sscanf(hit + strlen(key), "%d,%d", &a, &c) == 2 && (a == 1 || a == 2))
+      if (hit && (hit == e || hit[-1] == ';') && sscanf(hit + strlen(key), "%d,%d", &a, &c) == 2 && (a == 1 || a == 2) && a <= a_max)
         for (int x : nts) if (x == c) { wm = a; nt = c; forced = true; }
     }
   }
@@ -1088,8 +1092,8 @@ static int pick_nnb(const GemmNNB& g, hipStream_t st, int smin, int span) {
     // k=1 products carry a third of the MFMAs per weight byte: 64-row tiles (twice the weight traffic per MAC) lose at every
     // conv shape measured (256 -> 256, L=650: 28 us on 64 x 112 tiles, 20 us on 128 x 64); only the single-"batch" LSTM
     // product, short of workgroups, still wants them
-    const int a_min = (KT == 1 && g.B > 1 && !g.epi && g.M > 64) ? 2 : 1;
-    for (int a = a_min; a <= 2; ++a)
+    const int a_min = (KT == 1 && g.B > 1 && !g.epi && g.M > 64 && a_max == 2) ? 2 : 1;
+    for (int a = a_min; a <= a_max; ++a)
       for (int c : nts) {
         const long tiles = (long)ssv_cdiv(g.M, 64 * a) * ssv_cdiv(g.N, 16 * c) * g.B;
         const double per_tile = (double)a * c + 0.9 * a + 0.25 * c + 1.0;

@@ -115,6 +115,7 @@ struct GemmNNB {
   // GEMM's M axis, i.e. across workgroups; this makes the LayerNorm / gate forward a reduction-free streaming kernel):
   // colstats[((b * (M / 64) + m / 64) * N + n) * 2 + {0, 1}] = mean and sum of squared deviations of C(b, 64-row group, n)
   // over the group's 64 rows, bias included.  Needs M % 64 == 0, unit column stride, no LSTM epilogue.  Null: not wanted.
+  // (a row tile writes the groups it holds whole: with M % 128 == 64 pick_nnb takes 64-row tiles only)
   float* colstats = nullptr;
   // One output row beyond the last full 128-row tile, kept out of the MFMA tiles (gemm_nn_bf3w_kernel<.., XR = 1>, k = 1): M = 128 j + 1 output
   // rows -- the 513-channel layers of SSRN -- cost a whole extra row tile of MFMAs for ONE row otherwise.  xrow_w[k * xrow_sk], k < Kc, is that
