@@ -93,7 +93,9 @@ int ssv_conv1d_bwd_data(const float* dy, long dy_bs, const float* dy_amax, int d
                         int B, int Cin, int Cout, int L, int k, int dilation, int causal,
                         void* ws, size_t ws_bytes, ssv_stream_t stream);
 /* dw(o,c,j) = sum_{b,t} dy(b,o,t) x(b,c,t+(j-j0)*dilation); split over the batch into slabs, summed
- * in a fixed order (bitwise reproducible). */
+ * in a fixed order (bitwise reproducible).  With batch strides larger than C*L the kernels READ the floats between two items of dy and of x
+ * (their windows run past a row's end, never past the tensor's last element) and count them as zeros whatever they hold -- NaN, Inf or
+ * the gradient of the other half of a torch.cat; they write nothing outside dw and ws. */
 size_t ssv_conv1d_bwd_weight_workspace(int B, int Cin, int Cout, int L, int k);
 int ssv_conv1d_bwd_weight(const float* dy, long dy_bs, const float* dy_amax, int dy_namax, const float* x, long x_bs, const float* x_amax, int x_namax,
                           float* dw, int B, int Cin, int Cout, int L, int k, int dilation, int causal,
@@ -159,6 +161,7 @@ int ssv_pointwise_conv_ln_act_bwd(const float* dy, long dy_bs, const float* x, l
  * rows or NULL, pgrads (n2) out or NULL, shift[j] = (j - j0) * dilation as ssv_conv_shifts returns them.
  * max_shift: the caller's bound on |shift[j]| over all jobs (the table lives on the device; the entry plans its kernel from the
  * bound), or -1 for "unknown" (the general kernel).  A job whose shifts exceed a stated bound gets NaN gradients, not wrong ones.
+ * dy_bs / x_bs may exceed C*L: what lies between two items of a job's dy or x is read and counted as zeros, as in ssv_conv1d_bwd_weight.
  * Split-bf16 mode only, B*L >= 256 (ssv_conv1d_bwd_weight_multi_ok). */
 typedef struct {
   const float* dy; const float* x; float* dw; const float* part; float* pgrads;

@@ -100,19 +100,26 @@ __global__ __launch_bounds__(64 * WV, WV == 4 ? 2 : 1) void gemm_nt_bf3_kernel(c
   static_assert(!XR || (KT == 1 && WV == 4 && (256 % KG) == 0), "extra row: k = 1; a thread's slots share their k-group");
   const bool xr_on = XR && mt == 0;
   float xacc[XR ? NX : 1];
-  uint4 xra[XR ? 2 : 1];               // dH(M - 1, t0 + 8 kg .. + 7) of the tile in flight (raw; what lies past the row meets masked input)
+  uint4 xra[XR ? 2 : 1];               // dH(M - 1, t0 + 8 kg .. + 7) of the tile in flight (raw; an edge tile zeroes what lies past the row, see commitX)
 #pragma unroll
   for (int r = 0; r < (XR ? NX : 1); ++r) xacc[r] = 0.f;
   // dH fragments: two sets of (hi, lo) register tuples; set n & 1 is chunk n's.  The next chunk's windows are LOADED into the other
   // set (a window's two 16-byte loads = its two tuples) and split there in place, dword by dword (split8p's order of the time steps):
   // no staging registers.  (The split of the next set woven behind the MFMAs of a chunk's last tap -- one half-rate split instruction
   // hides behind a 16x16x32 MFMA of the same wave, tools/probe/mfma_valu.hip -- was built on this layout and measured: no change
-  // in-step, 268.5 vs 268.3 us; with two waves on a SIMD the other wave's MFMAs already fill those slots.)  dH needs no masks and no clamps:
+  // in-step, 268.5 vs 268.3 us; with two waves on a SIMD the other wave's MFMAs already fill those slots.)  dH needs no clamps, and a mask in an
+  // item's ragged last chunk only:
   //   * it is read by BUFFER loads whose range is the tensor (per-dword range check: what lies past the end reads 0; its offsets are
-  //     never negative), so a window may run past its row -- into the next row's values, or into zeros;
-  //   * time steps at or past the row length meet an input tile that is zero there (x_edge / the mask of the input include t < La).
-  //   (A NaN or Inf at the head of the NEXT row would so reach this row's sums as NaN; with masks it stayed in its own row.)
+  //     never negative), so a window may run past its row -- into the next row's values, into zeros, or, for an item's last row, into
+  //     whatever the caller keeps between two items (a batch-strided dy: the gradient of the other half of a torch.cat, say);
+  //   * time steps at or past the row length meet an input tile that is zero there (x_edge / the mask of the input include t < La), but
+  //     zero times what lies there is a sum only if that is finite AFTER the split: a gap value beyond the view's fp16 scale is Inf, a NaN
+  //     stays one.  splitA therefore zeroes t >= La in chunks that reach past the row (a wave-uniform test, as gemm_nt3r_kernel::splitA) --
+  //     in the waves whose windows can leave the item only: every other row runs on into the next rows of its own item, values of the tensor.
+  //     (From L = 64 on these are the waves that hold row M - 1; a shorter row's last chunk spans several rows.)
   uint4 AH[2][WM][KS], AL[2][WM][KS];
+  const int row_hi = min(m0 + (wave + 1) * WM * 16, p.M) - 1;                                   // the last row this wave reads (arow clamps to M - 1)
+  const bool last_rows = __builtin_amdgcn_readfirstlane(row_hi * (int)p.sam + tchunks * KB) > (p.M - 1) * (int)p.sam + p.La;      // its last chunk ends past the item
 
   // A window = 8 consecutive time steps of one row, at any alignment.  Element offsets are 32-bit (the launcher checks
   // that both tensors span < 2^30 elements): a per-thread row offset, fixed for the whole kernel, plus a wave-uniform
@@ -221,8 +228,22 @@ __global__ __launch_bounds__(64 * WV, WV == 4 ? 2 : 1) void gemm_nt_bf3_kernel(c
     v[0] = __builtin_bit_cast(float, t0_.x); v[1] = __builtin_bit_cast(float, t0_.y); v[2] = __builtin_bit_cast(float, t0_.z); v[3] = __builtin_bit_cast(float, t0_.w);
     v[4] = __builtin_bit_cast(float, t1_.x); v[5] = __builtin_bit_cast(float, t1_.y); v[6] = __builtin_bit_cast(float, t1_.z); v[7] = __builtin_bit_cast(float, t1_.w);
   };
-  auto splitA = [&](auto set) __attribute__((always_inline)) {                                             // AH / AL[set]: raw -> (hi, lo), in place
+  auto splitA = [&](auto set, int t0) __attribute__((always_inline)) {                                     // AH / AL[set]: raw -> (hi, lo), in place
     constexpr int SET = decltype(set)::value;
+    // (wave-uniform) the item's last chunk, the waves whose windows leave the item: time steps at or past the row length count as zeros.  The raw dwords are
+    // zeroed where they lie, in a pass of its own ahead of the split: inside the split loop the mask cost <1, 2, 8> the three registers it has left
+    if (__builtin_expect(last_rows && t0 + KB > p.La, 0)) {
+      const int nv = p.La - t0 - 8 * (int)((threadIdx.x >> 4) & 3u);      // valid steps from the lane's first window on
+#pragma unroll
+      for (int i = 0; i < WM; ++i)
+#pragma unroll
+        for (int s2 = 0; s2 < KS; ++s2) {
+          uint4& h = AH[SET][i][s2];
+          uint4& l = AL[SET][i][s2];
+          h.x = 32 * s2 + 0 < nv ? h.x : 0u; h.y = 32 * s2 + 1 < nv ? h.y : 0u; h.z = 32 * s2 + 2 < nv ? h.z : 0u; h.w = 32 * s2 + 3 < nv ? h.w : 0u;
+          l.x = 32 * s2 + 4 < nv ? l.x : 0u; l.y = 32 * s2 + 5 < nv ? l.y : 0u; l.z = 32 * s2 + 6 < nv ? l.z : 0u; l.w = 32 * s2 + 7 < nv ? l.w : 0u;
+        }
+    }
 #pragma unroll
     for (int i = 0; i < WM; ++i)
 #pragma unroll
@@ -270,7 +291,11 @@ __global__ __launch_bounds__(64 * WV, WV == 4 ? 2 : 1) void gemm_nt_bf3_kernel(c
           if (!edge) {
 #pragma unroll
             for (int i = 0; i < 8; ++i) xv[i] = rx[r][i];
-          } else edge_vals(rx[r], mx[r], xv);
+          } else {
+            edge_vals(rx[r], mx[r], xv);
+#pragma unroll
+            for (int i = 0; i < 8; ++i) av[i] = ((mx[r] >> i) & 1) ? av[i] : 0.f;      // where the input is masked (t >= La among it) dH is not this row's
+          }
 #pragma unroll
           for (int i = 0; i < 8; ++i) xacc[r] = __builtin_fmaf(av[i], xv[i], xacc[r]);
         }
@@ -356,7 +381,7 @@ __global__ __launch_bounds__(64 * WV, WV == 4 ? 2 : 1) void gemm_nt_bf3_kernel(c
       // vmcnt(5) .. vmcnt(0) right after those loads, i.e. every step ended by waiting for the tile it had just requested.  With the k-steps multiplied
       // past a ragged row end (above) the loop's waits are counted again (tools/isa_loop_waits.py, profiles/round6_nt_bf3_waits.txt): in-step
       // 118.0 -> 116.8, 28.1 -> 27.7 us -- two workgroups per CU had been covering most of it.
-      if (j == KT - 1 && more) splitA(NXT{});
+      if (j == KT - 1 && more) splitA(NXT{}, ct0[1]);
       NT_STAMP(3);
       if (STEADY || s + 2 < steps) loadX(cb[c2], ct0[c2], j2);
       NT_STAMP(4);
@@ -373,7 +398,7 @@ __global__ __launch_bounds__(64 * WV, WV == 4 ? 2 : 1) void gemm_nt_bf3_kernel(c
     loadA(P0{}, cb[0], ct0[0]);
     loadX(cb[0], ct0[0], 0);
     scales();
-    splitA(P0{});
+    splitA(P0{}, ct0[0]);
     commitX(P0{}, ct0[0], 0);
     if (steps > 1) loadX(cb[1 / KT], ct0[1 / KT], 1 % KT);
     __syncthreads();

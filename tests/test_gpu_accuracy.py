@@ -193,7 +193,9 @@ def test_weight_gradient_ring_kernel_ragged_shapes_dilations_and_item_boundaries
     transposed reads at shifted rows (round 4).  What can go wrong there is all about edges: rows before an item's first and past its last
     time step (zeros of the convolution's padding), the virtual time line running from one batch item into the next, ring wrap-around
     (the mirror rows), row lengths that are multiples of nothing, channel and row tiles partly empty, the longest shifts the entry takes
-    (54: dilation 27, causal) -- each against float64 autograd of nn.Conv1d's expression (models/TTSModel.py:59-61, :78)."""
+    (54: dilation 27, causal) -- each against float64 autograd of nn.Conv1d's expression (models/TTSModel.py:59-61, :78).  Per tap and in L2
+    here; tests/test_gpu_wgrad_tiles.py holds the ring kernel per element (its "ring" rows and job tables: L + max_shift == 128, 20 chunks in
+    one slab, NaN gaps between the items, guard zones around dw and the workspace)."""
     gen = torch.Generator().manual_seed(21)
     for (B, Cin, Cout, L, d, causal) in RING_SHAPES:
         x = torch.randn(B, Cin, L, generator=gen)
@@ -303,7 +305,9 @@ def test_one_by_one_convolutions_with_128_j_plus_1_output_rows(B, Cin, Cout, L):
     extra-row forward / data-gradient kernel gemm_nn_bf3w_kernel<.., XR = 1> is held by WIDE_CASES of tests/test_gpu_conv_tiles.py (both split
     modes, the last row on its own) and by the B = 32 rows of tests/test_gpu_bench_shapes.py.  Forward, data gradient (whose output rows are
     the INPUT channels) and weight gradient against float64, at ragged lengths and channel counts (more slabs than chunks at L = 64, item
-    boundaries inside every range), and the last row on its own (where a wrong row would hide in an L2 norm over 513 rows)."""
+    boundaries inside every range), and the last row on its own (where a wrong row would hide in an L2 norm over 513 rows).  The weight-gradient
+    kernel is held per element by the "k1_128x96_xrow" rows of tests/test_gpu_wgrad_tiles.py (forced slab counts: ranges that start mid-item,
+    a slab that owns no chunk)."""
     gen = torch.Generator().manual_seed(B * 1000 + Cin + Cout + L)
     x = torch.randn(B, Cin, L, generator=gen)
     w = torch.randn(Cout, Cin, 1, generator=gen) * 0.05
@@ -326,7 +330,8 @@ def test_one_by_one_weight_gradient_on_the_large_output_tiles(B, Cin, Cout, L):
     """k = 1 weight gradients whose output is 2^21 elements or more with whole 128-row / 128-column tiles -- the shape class of the GE2E embedder's LSTM
     weight gradients (GE2E/speech_embedder_net.py:19: 3072 x 768 over 120 frames x 880 utterances), reached here through the convolution entry: the
     256 x 128 tile on 8 waves (Cout % 256 == 0) and the 128 x 128 tile (Cout % 256 == 128), with the column tiles of a row tile adjacent
-    (csrc/wgrad_nt.hip, ssv_nt_bf3_tile and the tile order).  Ragged lengths, more tiles than one XCD holds, against float64."""
+    (csrc/wgrad_nt.hip, ssv_nt_bf3_tile and the tile order).  Ragged lengths, more tiles than one XCD holds, against float64.  Both tiles are held
+    per element by the "k1_128x128" and "k1_256x128_w8" rows of tests/test_gpu_wgrad_tiles.py (64, 66 and 129 tiles: both tile orders)."""
     gen = torch.Generator().manual_seed(B * 1000 + Cin + Cout + L)
     x = torch.randn(B, Cin, L, generator=gen)
     w = torch.randn(Cout, Cin, 1, generator=gen) * 0.05
