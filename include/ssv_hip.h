@@ -531,6 +531,57 @@ int ssv_gmm_diag_update(const double* stats, double* w, double* mu, double* var,
                         double min_count, double min_weight, ssv_stream_t stream);
 int ssv_gmm_diag_planes(const double* w, const double* mu, const double* var, float* A, float* B, float* g, int C, int D, ssv_stream_t stream);
 
+/* ---- I-vector extractor: total-variability EM, extraction, cosine trials (additions; ABI version unchanged) ----
+ * The middle of kaldi_ivectors/run.sh (extractor training, i-vector extraction, trial scores) on the Baum-Welch statistics above.  The
+ * model is OURS, stated here; Kaldi's ivector-extractor-* binaries (prior offset, weight projection, full covariances) are NOT reproduced
+ * and there is no PLDA: scoring is cosine on length-normalised vectors.  All arithmetic is independent of ssv_set_precision; no float
+ * atomics; the order of every sum follows from the shapes alone.  Bad arguments: -1; a shape beyond a kernel: -2; both before any launch.
+ * Limits of every entry that takes them: 1 <= R <= 192 (the packed float64 triangle of R = 192, 148,224 bytes, is the most one
+ * workgroup's LDS holds), C <= 2048, D <= 128.
+ *
+ * Notation: UBM of C Gaussians in D dimensions (mu, var (C, D) float64); rank R, P = R (R + 1) / 2; T (C, D, R) float64.  A symmetric
+ * R x R matrix is PACKED as its lower triangle, row-major: element (i, j), j <= i, at i (i + 1) / 2 + j.
+ *
+ * ssv_ivec_tv_planes: G (C * D, R) float32 = diag(1 / var_c) T_c and Pk (C, P) float32 = packed T_c^T diag(1 / var_c) T_c, summed over d
+ * in double and rounded once.
+ * ssv_ivec_centre_stats: Ft (U, C, D) = F - N mu, one float32 fused multiply-add per element (mu rounded once); Ft may be F. */
+int ssv_ivec_tv_planes(const double* T, const double* var, float* G, float* Pk, int C, int D, int R, ssv_stream_t stream);
+int ssv_ivec_centre_stats(const float* N, const float* F, const double* mu, float* Ft, long U, int C, int D, ssv_stream_t stream);
+/* The product family, on v_mfma_f32_16x16x4_f32 (exact fp32 fma chains), all operands row-major:
+ *   ssv_ivec_product:     out (m, n) float32 = A (m, K) B (K, n), rounded once;
+ *   ssv_ivec_product_tn:  acc (m, n) float64 += A (U, m)^T B (U, n)  (K = U; acc persists across the passes of an accumulation).
+ * K is walked in runs of ssv_ivec_product_run() = 256 elements, each an fp32 chain from zero accumulators, and the runs are added in
+ * double registers: a single fp32 chain over K = C D = 61,440 would cost more digits than a blocked float32 product does.  Every
+ * output element belongs to one workgroup (a tile of ssv_ivec_product_tile() = 64 rows and columns); the order of its sum depends on K
+ * alone, so a row of the output does not depend on the rows that share its launch.  Used as Lp (U, P) = N Pk, b (U, R) = Ft G,
+ * A (C, P) += N^T M, Cm (C D, R) += Ft^T w, Nc (C, 1) += N^T 1.  More than 65535 x 64 rows: -2. */
+int ssv_ivec_product_run(void);
+int ssv_ivec_product_tile(void);
+int ssv_ivec_product(const float* A, const float* B, float* out, long m, long n, long K, ssv_stream_t stream);
+int ssv_ivec_product_tn(const float* A, const float* B, double* acc, long U, long m, long n, ssv_stream_t stream);
+/* E-step, a workgroup per utterance, in double on the packed triangle in LDS:  L_u = I + unpack(Lp_u),  w_u = L_u^-1 b_u (Cholesky, the
+ * forward substitution on the way, then the back substitution),  obj_u = -1/2 log|L_u| + 1/2 b_u . w_u -- with posteriors and covariances
+ * fixed, the utterance's marginal log-likelihood up to a constant in T -- and, when M is not NULL (training), the inverse in place
+ * (LAPACK's trtri + lauum forms) and M_u = L_u^-1 + w_u w_u^T, packed.  w (U, R), M (U, P) float32, obj (U) float64.  M == NULL: nothing of M
+ * is touched and w, obj are the same bits.  A pivot that is not positive cannot happen for N >= 0 (L >= I); met anyway (NaN input), the
+ * utterance's w, obj and M are NaN and nothing else is touched. */
+int ssv_ivec_estep(const float* Lp, const float* b, float* w, float* M, double* obj, long U, int R, ssv_stream_t stream);
+/* M-step, a workgroup per Gaussian, all in float64:  T_c <- Cm_c A_c^-1 (A_c (P) packed, inverted in LDS by the E-step's functions; the D
+ * rows of Cm_c stream past it), then T_c <- T_c J when J (R, R) is not NULL (the minimum-divergence step; J = chol_lower(mean M_u),
+ * factorised by the caller).  A Gaussian with Nc[c] < min_count (or Nc[c] <= 0) keeps its T_c bit for bit -- J included; the project's own
+ * rule, as for the starved Gaussian of ssv_gmm_diag_update.  A (C, P), Cm (C D, R), Nc (C) float64 as ssv_ivec_product_tn accumulates them;
+ * T (C, D, R) IN / OUT. */
+int ssv_ivec_tv_update(const double* A, const double* Cm, const double* Nc, const double* J, double* T, int C, int D, int R, double min_count,
+                       ssv_stream_t stream);
+/* Cosine trials in one launch: enroll (n_enroll, R), evalv (E, R) float32; spk_off (S + 1) int64 DEVICE, speaker s owning the enrolment
+ * rows [spk_off[s], spk_off[s+1]) (spk_off_host: the same table as a HOST array or NULL; when given, checked here -- ascending, inside
+ * [0, n_enroll], else -1; the device clamps what it reads and takes a descending pair as empty).  Every vector is length-normalised
+ * (norm 0: the zero vector), a speaker model is the mean of its normalised enrolment vectors, normalised again and kept as float32 in
+ * LDS, and scores (E, S) float32 = their dot products, summed in double and rounded once.  A zero vector, or a speaker without enrolment,
+ * scores 0, never NaN.  S R 4 bytes beyond 128 KiB of LDS: -2. */
+int ssv_ivec_cosine_trials(const float* enroll, const long* spk_off, const long* spk_off_host, const float* evalv, float* scores, long n_enroll, int S,
+                           long E, int R, ssv_stream_t stream);
+
 /* ---- Vocoder and spectrogram front end ------------------------------------------------
  * Replaces the CPU tail of synthesis, synthesize.py:138-147 / generate_test_utterances.py:128-139
  * (`librosa.core.griffinlim(S, n_iter=64, hop_length, win_length)`, `signal.lfilter([1], [1, -PREEMPH], y)`, peak

@@ -91,3 +91,70 @@ extern "C" int ssv_gmm_diag_planes(const double* w, const double* mu, const doub
   SSV_TRY(gmm_cd_ok("gmm_diag_planes", C, D));
   return ivec_launch_update(nullptr, w, nullptr, (double*)mu, (double*)var, A, B, g, C, D, 1.0, 0.0, 0.5, (hipStream_t)stream);
 }
+
+// ---- the i-vector extractor (include/ssv_hip.h, "I-vector extractor"): kernels and tile limits in ivector_tv.hip -------------------------
+#pragma GCC visibility push(hidden)      // defined in ivector_tv.hip
+int tv_launch_planes(const double* T, const double* var, float* G, float* Pk, int C, int D, int R, hipStream_t st);
+int tv_launch_centre(const float* N, const float* F, const double* mu, float* Ft, long U, int C, int D, hipStream_t st);
+int tv_launch_product(const float* A, const float* B, float* out, long m, long n, long K, hipStream_t st);
+int tv_launch_product_tn(const float* A, const float* B, double* acc, long U, long m, long n, hipStream_t st);
+int tv_launch_estep(const float* Lp, const float* b, float* w, float* M, double* obj, long U, int R, hipStream_t st);
+int tv_launch_update(const double* A, const double* Cm, const double* Nc, const double* J, double* T, int C, int D, int R, double min_count, hipStream_t st);
+int tv_launch_cosine(const float* enroll, const long* spk_off, const float* evalv, float* scores, long n_enroll, int S, long E, int R, hipStream_t st);
+#pragma GCC visibility pop
+
+extern "C" int ssv_ivec_tv_planes(const double* T, const double* var, float* G, float* Pk, int C, int D, int R, ssv_stream_t stream) {
+  SSV_CHECK(T && var && G && Pk, SSV_BAD_SHAPE, "ivec_tv_planes: null pointer (T, var, G and Pk are required)");
+  SSV_CHECK(C >= 1 && D >= 1 && R >= 1, SSV_BAD_SHAPE, "ivec_tv_planes: need C >= 1, D >= 1 and R >= 1; got C=%d D=%d R=%d", C, D, R);
+  return tv_launch_planes(T, var, G, Pk, C, D, R, (hipStream_t)stream);
+}
+
+extern "C" int ssv_ivec_centre_stats(const float* N, const float* F, const double* mu, float* Ft, long U, int C, int D, ssv_stream_t stream) {
+  SSV_CHECK(N && F && mu && Ft, SSV_BAD_SHAPE, "ivec_centre_stats: null pointer (N, F, mu and Ft are required)");
+  SSV_CHECK(U >= 1 && C >= 1 && D >= 1, SSV_BAD_SHAPE, "ivec_centre_stats: need U >= 1, C >= 1 and D >= 1; got U=%ld C=%d D=%d", U, C, D);
+  return tv_launch_centre(N, F, mu, Ft, U, C, D, (hipStream_t)stream);
+}
+
+extern "C" int ssv_ivec_product_run(void) { return 256; }
+extern "C" int ssv_ivec_product_tile(void) { return 64; }
+
+extern "C" int ssv_ivec_product(const float* A, const float* B, float* out, long m, long n, long K, ssv_stream_t stream) {
+  SSV_CHECK(A && B && out, SSV_BAD_SHAPE, "ivec_product: null pointer (A, B and out are required)");
+  SSV_CHECK(m >= 1 && n >= 1 && K >= 1, SSV_BAD_SHAPE, "ivec_product: need m >= 1, n >= 1 and K >= 1; got m=%ld n=%ld K=%ld", m, n, K);
+  return tv_launch_product(A, B, out, m, n, K, (hipStream_t)stream);
+}
+
+extern "C" int ssv_ivec_product_tn(const float* A, const float* B, double* acc, long U, long m, long n, ssv_stream_t stream) {
+  SSV_CHECK(A && B && acc, SSV_BAD_SHAPE, "ivec_product_tn: null pointer (A, B and acc are required)");
+  SSV_CHECK(U >= 1 && m >= 1 && n >= 1, SSV_BAD_SHAPE, "ivec_product_tn: need U >= 1, m >= 1 and n >= 1; got U=%ld m=%ld n=%ld", U, m, n);
+  return tv_launch_product_tn(A, B, acc, U, m, n, (hipStream_t)stream);
+}
+
+extern "C" int ssv_ivec_estep(const float* Lp, const float* b, float* w, float* M, double* obj, long U, int R, ssv_stream_t stream) {
+  SSV_CHECK(Lp && b && w && obj, SSV_BAD_SHAPE, "ivec_estep: null pointer (Lp, b, w and obj are required; M is optional)");
+  SSV_CHECK(U >= 1 && R >= 1, SSV_BAD_SHAPE, "ivec_estep: need U >= 1 and R >= 1; got U=%ld R=%d", U, R);
+  return tv_launch_estep(Lp, b, w, M, obj, U, R, (hipStream_t)stream);
+}
+
+extern "C" int ssv_ivec_tv_update(const double* A, const double* Cm, const double* Nc, const double* J, double* T, int C, int D, int R, double min_count,
+                                  ssv_stream_t stream) {
+  SSV_CHECK(A && Cm && Nc && T, SSV_BAD_SHAPE, "ivec_tv_update: null pointer (A, Cm, Nc and T are required; J is optional)");
+  SSV_CHECK(C >= 1 && D >= 1 && R >= 1 && min_count >= 0.0, SSV_BAD_SHAPE, "ivec_tv_update: need C >= 1, D >= 1, R >= 1 and min_count >= 0; got C=%d D=%d R=%d min_count=%g",
+            C, D, R, min_count);
+  return tv_launch_update(A, Cm, Nc, J, T, C, D, R, min_count, (hipStream_t)stream);
+}
+
+extern "C" int ssv_ivec_cosine_trials(const float* enroll, const long* spk_off, const long* spk_off_host, const float* evalv, float* scores, long n_enroll, int S,
+                                      long E, int R, ssv_stream_t stream) {
+  SSV_CHECK(enroll && spk_off && evalv && scores, SSV_BAD_SHAPE, "ivec_cosine_trials: null pointer (enroll, spk_off, evalv and scores are required)");
+  SSV_CHECK(n_enroll >= 1 && S >= 1 && E >= 1 && R >= 1, SSV_BAD_SHAPE, "ivec_cosine_trials: need n_enroll >= 1, S >= 1, E >= 1 and R >= 1; got n_enroll=%ld S=%d E=%ld R=%d",
+            n_enroll, S, E, R);
+  if (spk_off_host) {
+    SSV_CHECK(spk_off_host[0] >= 0 && spk_off_host[S] <= n_enroll, SSV_BAD_SHAPE, "ivec_cosine_trials: speakers [%ld, %ld) leave the %ld enrolment vectors",
+              spk_off_host[0], spk_off_host[S], n_enroll);
+    for (int s = 0; s < S; ++s)
+      SSV_CHECK(spk_off_host[s] <= spk_off_host[s + 1], SSV_BAD_SHAPE, "ivec_cosine_trials: spk_off descends at speaker %d (%ld > %ld)", s, spk_off_host[s],
+                spk_off_host[s + 1]);
+  }
+  return tv_launch_cosine(enroll, spk_off, evalv, scores, n_enroll, S, E, R, (hipStream_t)stream);
+}

@@ -599,6 +599,32 @@ def ivector_curve(score_file, enroll_utt_num=3, eval_utt_num=20, thresholds=None
     return dict(thresholds=thresholds, spoof_rate=counts[:, 1].astype(np.int64) / L, gt_frr=1 - counts[:, 0].astype(np.int64) / L, counts=counts)
 
 
+def ivector_trials(enroll, enroll_utt2spk, evalv, eval_utt2spk, score_file, thresholds, enroll_utt_num=3, eval_utt_num=20):
+    """The trials of the i-vector system without Kaldi: ``enroll`` (n, R) and ``evalv`` (E, R) float32 device i-vectors with their
+    '<utterance> <speaker>' lines (``ivector.split_enroll_eval`` order: a speaker's enrolment rows are consecutive), scored by cosine on the
+    device (``ivector.cosine_trials``), written to ``score_file`` in ``trial_list`` order as '<speaker> <utterance> <score>', and swept by
+    ``ivector_curve(score_file, thresholds=thresholds)``, whose dict is returned with ``scores`` (E, S) and ``speakers`` added.
+    ``thresholds`` is required: ``curve_thresholds("ivector")`` spans PLDA's range, cosine scores lie in [-1, 1]."""
+    from . import ivector
+    en, ev = ivector._utt2spk(enroll_utt2spk, "ivector_trials"), ivector._utt2spk(eval_utt2spk, "ivector_trials")
+    if len(en) != enroll.shape[0] or len(ev) != evalv.shape[0]:
+        raise ValueError("ivector_trials: %d enrolment lines for %d vectors, %d eval lines for %d vectors" % (len(en), enroll.shape[0], len(ev), evalv.shape[0]))
+    speakers, off = [], [0]
+    for i, (_, spk) in enumerate(en):
+        if not speakers or spk != speakers[-1]:
+            if spk in speakers:
+                raise ValueError("ivector_trials: the enrolment rows of speaker %s are not consecutive" % spk)
+            if speakers:
+                off.append(i)
+            speakers.append(spk)
+    off.append(len(en))
+    scores = ivector.cosine_trials(enroll, off, evalv)
+    ivector.write_trial_scores(score_file, speakers, [utt for utt, _ in ev], scores)
+    out = ivector_curve(score_file, enroll_utt_num, eval_utt_num, thresholds, device=enroll.device)
+    out.update(scores=scores, speakers=speakers)
+    return out
+
+
 def ivector_spoofrate(score_file, thres, train_spk_num=88, enroll_utt_num=3, eval_utt_num=20, device="cuda"):
     """kaldi_ivectors/ivector_spoofrate.py whole: the spoofing own-speaker trials of a score file accepted at ``thres`` (score > thres in
     float64; counted by the list entry with one threshold), over total_num = (lines / 2) // (108 - train_spk_num), which must equal

@@ -1,5 +1,5 @@
-"""The front half of the i-vector system on the device: cepstral features, a diagonal-covariance GMM-UBM trained by EM, and the
-Baum-Welch statistics (zeroth and first order, per utterance) that i-vector training and extraction start from.
+"""The i-vector system on the device: cepstral features, a diagonal-covariance GMM-UBM trained by EM, the Baum-Welch statistics (zeroth
+and first order, per utterance), the total-variability extractor trained by EM on them, i-vector extraction and cosine trial scores.
 
 This is the bottom of the reference's ``kaldi_ivectors/run.sh`` (MFCC -> VAD -> diagonal UBM -> full UBM -> extractor -> PLDA), as far
 as the diagonal UBM.  Kaldi's binaries are NOT reproduced: its MFCC (povey window, snip-edges, energy in C0), its energy VAD and the
@@ -7,7 +7,12 @@ recipe's ``conf/`` values are not pinned here; the algorithms are the ones state
 restatement (``tests/_ivector_ref.py``) is the yardstick.  Ours, not Kaldi's: the initialisation of ``DiagUbm.from_frames`` and the
 treatment of a starved Gaussian in the M-step.
 
-Every FLOP of the hot path runs in ``csrc/ivector.hip``; torch is plumbing (memory, the stream).  Tensors must live on a ROCm device.
+The extractor (``TotalVariability``) is this project's model too, stated at the entries of ``include/ssv_hip.h`` ("I-vector extractor"):
+no prior offset, no weight projection, no full covariances, no PLDA -- scoring is cosine on length-normalised vectors -- and its yardstick
+is ``tests/_ivector_tv_ref.py``.
+
+Every FLOP of the hot path runs in ``csrc/ivector.hip`` and ``csrc/ivector_tv.hip``; torch is plumbing (memory, the stream).  Tensors must
+live on a ROCm device.
 """
 import ctypes
 from types import SimpleNamespace
@@ -19,7 +24,7 @@ from . import _lib, ops
 from .ops import _p
 
 _F32, _F64, _I32, _I64 = torch.float32, torch.float64, torch.int32, torch.int64
-MAX_D, MAX_C, MAX_NSEL = 128, 2048, 32
+MAX_D, MAX_C, MAX_NSEL, MAX_R = 128, 2048, 32, 192
 LL_ROW = 4096          # the per-frame log-likelihoods are summed as rows of this many columns (ssv_gmm_stats_reduce), then over the columns
 
 
@@ -327,3 +332,340 @@ def train_diag_ubm(front_end, y16, lengths, spans=None, num_gauss=1024, seed=0, 
     X = cepstral_features(mel, utt_off, n_ceps, lifter, delta_window, delta_order, cmn_window)[:pl.n_frames]
     ubm = DiagUbm.from_frames(X, num_gauss, seed)
     return SimpleNamespace(ubm=ubm, history=ubm.fit(X, **fit_kw), features=X, utt_off=utt_off)
+
+
+# ------------------------------------------------------------------------------------------------------------ the packed triangle
+def tri_size(R):
+    return R * (R + 1) // 2
+
+
+def tri_pack(S):
+    """(..., R, R) -> (..., P): the lower triangle row-major, element (i, j), j <= i, at i (i + 1) / 2 + j (host arrays)."""
+    S = np.asarray(S)
+    i, j = np.tril_indices(S.shape[-1])
+    return np.ascontiguousarray(S[..., i, j])
+
+
+def tri_unpack(p, R=None):
+    """(..., P) -> (..., R, R) symmetric (host arrays); P must be a triangular number (and R's, when R is given)."""
+    p = np.asarray(p)
+    n = int(round((np.sqrt(8.0 * p.shape[-1] + 1.0) - 1.0) / 2.0))
+    if tri_size(n) != p.shape[-1] or (R is not None and n != R):
+        raise ValueError("tri_unpack: %d entries are not the lower triangle of a %s x %s matrix" % (p.shape[-1], R or "R", R or "R"))
+    i, j = np.tril_indices(n)
+    S = np.zeros(p.shape[:-1] + (n, n), dtype=p.dtype)
+    S[..., i, j] = p
+    S[..., j, i] = p
+    return S
+
+
+# ------------------------------------------------------------------------------------------------------------ the extractor
+def _stats_pair(N, Ft, C, D, who):
+    N = _matrix(N, who + ": N", cols=C)
+    if not isinstance(Ft, torch.Tensor):
+        raise ValueError("%s: Ft: need a torch tensor, got %s" % (who, type(Ft).__name__))
+    ops._dev(Ft, who + ": Ft")
+    if Ft.dtype != _F32 or Ft.numel() != N.shape[0] * C * D or Ft.shape[0] != N.shape[0]:
+        raise ValueError("%s: Ft: need float32 (%d, %d, %d), got %s %s" % (who, N.shape[0], C, D, Ft.dtype, tuple(Ft.shape)))
+    return N, Ft.contiguous().view(N.shape[0], C * D)
+
+
+def centre_stats(ubm, N, F, out=None):
+    """``Ft`` (U, C, D) = ``F`` - ``N`` mu, one float32 fused multiply-add per element (``ssv_ivec_centre_stats``): the first-order
+    statistics centred on the UBM's means BEFORE any product, so that the big product does not cancel.  ``out``: where to write (``F``
+    itself is allowed); default a new tensor.  ``ubm``: a ``DiagUbm`` or a ``TotalVariability``."""
+    C, D = ubm.mu.shape
+    N, F2 = _stats_pair(N, F, C, D, "centre_stats")
+    ops._dev(ubm.mu, "centre_stats: mu")
+    if out is None:
+        out = torch.empty((N.shape[0], C, D), dtype=_F32, device=N.device)
+    elif out.dtype != _F32 or out.numel() != F2.numel() or not out.is_contiguous() or not out.is_cuda:
+        raise ValueError("centre_stats: out must be a contiguous float32 device tensor of F's size")
+    _lib.call("ssv_ivec_centre_stats", _p(N), _p(F2), _p(ubm.mu), _p(out), N.shape[0], C, D, ops._stream())
+    return out.view(N.shape[0], C, D)
+
+
+def product(A, B, out=None):
+    """``out`` (m, n) float32 = ``A`` (m, K) ``B`` (K, n) on the exact-fp32 MFMA, K in runs added in double (``ssv_ivec_product``)."""
+    A, B = _matrix(A, "product: A"), _matrix(B, "product: B")
+    if A.shape[1] != B.shape[0]:
+        raise ValueError("product: A is %s and B is %s" % (tuple(A.shape), tuple(B.shape)))
+    if out is None:
+        out = torch.empty((A.shape[0], B.shape[1]), dtype=_F32, device=A.device)
+    elif out.dtype != _F32 or tuple(out.shape) != (A.shape[0], B.shape[1]) or not out.is_contiguous() or not out.is_cuda:
+        raise ValueError("product: out must be a contiguous float32 device tensor (%d, %d)" % (A.shape[0], B.shape[1]))
+    _lib.call("ssv_ivec_product", _p(A), _p(B), _p(out), A.shape[0], B.shape[1], A.shape[1], ops._stream())
+    return out
+
+
+def product_tn(A, B, acc):
+    """``acc`` (m, n) float64 += ``A`` (U, m)^T ``B`` (U, n), in place (``ssv_ivec_product_tn``)."""
+    A, B = _matrix(A, "product_tn: A"), _matrix(B, "product_tn: B")
+    if not isinstance(acc, torch.Tensor) or not acc.is_cuda or acc.dtype != _F64 or not acc.is_contiguous() or A.shape[0] != B.shape[0] \
+            or acc.numel() != A.shape[1] * B.shape[1]:
+        raise ValueError("product_tn: A %s, B %s need a contiguous float64 device accumulator of %d x %d" % (tuple(A.shape), tuple(B.shape), A.shape[1], B.shape[1]))
+    _lib.call("ssv_ivec_product_tn", _p(A), _p(B), _p(acc), A.shape[0], A.shape[1], B.shape[1], ops._stream())
+    return acc
+
+
+def plan_tv_passes(U, C, D, R, free, train):
+    """Host planning of the extractor's passes over ``U`` utterances whose statistics are resident: a pass [u0, u1) holds per utterance
+    Lp (P floats; training: M as well), b and w (R floats each), obj (a double) and, training, a one -- at most half of what is left of
+    ``free`` after the fixed part: training, the float64 accumulators A (C, P), Cm (C D, R), Nc (C) and sum M (P); extraction, the
+    output w (U, R).  Returns (passes, need): ``need`` = the fixed part plus one utterance, the least ``free`` with which a plan exists."""
+    U, P = int(U), tri_size(int(R))
+    if U < 1:
+        raise ValueError("plan_tv_passes: need at least one utterance")
+    per = P * 4 * (2 if train else 1) + R * 8 + 8 + (4 if train else 0)
+    fixed = (C * P + C * D * R + C + P) * 8 if train else U * R * 4
+    n = max(1, min(U, ((int(free) - fixed) // 2) // per))
+    return [(u0, min(u0 + n, U)) for u0 in range(0, U, n)], fixed + per
+
+
+def plan_extract_passes(frames_per_utt, C, D, R, nsel, free):
+    """Host planning of ``extract_ivectors``: a pass [u0, u1) holds the sparse posteriors of its frames (nsel * 8 + 4 bytes a frame) and per
+    utterance the slab, N and Ft (2 C (1 + D) floats), Lp (P floats), b (R floats) and obj -- at most half of what is left of ``free``
+    after the output w (U, R).  Returns (passes, need), ``need`` = the output plus twice the costliest single utterance."""
+    n = [int(v) for v in frames_per_utt]
+    if not n or min(n) < 0:
+        raise ValueError("plan_extract_passes: need at least one utterance and no negative length")
+    row = 2 * C * (1 + D) * 4 + tri_size(int(R)) * 4 + R * 4 + 8
+    cost = [f * (nsel * 8 + 4) + row for f in n]
+    out_bytes = len(n) * R * 4
+    need = out_bytes + 2 * max(cost)
+    budget = max((int(free) - out_bytes) // 2, max(cost))
+    passes, u0, acc = [], 0, 0
+    for u, c in enumerate(cost):
+        if u > u0 and acc + c > budget:
+            passes.append((u0, u))
+            u0, acc = u, 0
+        acc += c
+    passes.append((u0, len(n)))
+    return passes, need
+
+
+class TotalVariability:
+    """A total-variability model on one device: ``T`` (C, D, R) float64 and the UBM it stands on (``w`` (C,), ``mu``, ``var`` (C, D)
+    float64), with the float32 planes ``G`` (C D, R) and ``Pk`` (C, P) the products read, rebuilt after every update."""
+
+    def __init__(self, T, w, mu, var):
+        for t, name in ((T, "T"), (w, "w"), (mu, "mu"), (var, "var")):
+            if not isinstance(t, torch.Tensor):
+                raise ValueError("TotalVariability: %s must be a torch tensor" % name)
+        if T.dim() != 3 or mu.dim() != 2 or tuple(T.shape[:2]) != tuple(mu.shape) or var.shape != mu.shape or w.shape != (mu.shape[0],) \
+                or any(t.dtype != _F64 for t in (T, w, mu, var)):
+            raise ValueError("TotalVariability: need float64 T (C, D, R), w (C,), mu (C, D), var (C, D); got %s %s, %s %s, %s %s, %s %s"
+                             % (T.dtype, tuple(T.shape), w.dtype, tuple(w.shape), mu.dtype, tuple(mu.shape), var.dtype, tuple(var.shape)))
+        C, D, R = T.shape
+        if not (1 <= C <= MAX_C and 1 <= D <= MAX_D and 1 <= R <= MAX_R):
+            raise ValueError("TotalVariability: C=%d must lie in [1, %d], D=%d in [1, %d] and R=%d in [1, %d]" % (C, MAX_C, D, MAX_D, R, MAX_R))
+        if any(t.device != T.device for t in (w, mu, var)):
+            raise ValueError("TotalVariability: T, w, mu and var must live on one device")
+        self.T, self.w, self.mu, self.var = (t.contiguous().clone() for t in (T, w, mu, var))
+        self._planes = self._ubm = None
+
+    C = property(lambda self: self.T.shape[0])
+    D = property(lambda self: self.T.shape[1])
+    R = property(lambda self: self.T.shape[2])
+    P = property(lambda self: tri_size(self.T.shape[2]))
+    device = property(lambda self: self.T.device)
+
+    def planes(self):
+        """(G, Pk) of the current ``T`` (``ssv_ivec_tv_planes``): built at first use, rebuilt by every update."""
+        if self._planes is None:
+            for t, name in ((self.T, "T"), (self.var, "var")):
+                ops._dev(t, "TotalVariability: " + name)
+            G = torch.empty((self.C * self.D, self.R), dtype=_F32, device=self.device)
+            Pk = torch.empty((self.C, self.P), dtype=_F32, device=self.device)
+            _lib.call("ssv_ivec_tv_planes", _p(self.T), _p(self.var), _p(G), _p(Pk), self.C, self.D, self.R, ops._stream())
+            self._planes = (G, Pk)
+        return self._planes
+
+    G = property(lambda self: self.planes()[0])
+    Pk = property(lambda self: self.planes()[1])
+
+    def ubm(self):
+        if self._ubm is None:
+            self._ubm = DiagUbm(self.w, self.mu, self.var)
+        return self._ubm
+
+    # ------------------------------------------------------------------ state
+    def state_dict(self):
+        return {"T": self.T.clone(), "w": self.w.clone(), "mu": self.mu.clone(), "var": self.var.clone()}
+
+    def save(self, path):
+        """``.npz`` with the float64 ``T``, ``w``, ``mu``, ``var`` (the planes are derived)."""
+        np.savez(path, **{k: v.cpu().numpy() for k, v in self.state_dict().items()})
+
+    @classmethod
+    def load(cls, path, device="cuda"):
+        """``device="cpu"`` gives a state holder only; the operations need a ROCm device."""
+        with np.load(path) as z:
+            return cls(*(torch.from_numpy(np.asarray(z[k], dtype=np.float64)).to(device) for k in ("T", "w", "mu", "var")))
+
+    @classmethod
+    def from_ubm(cls, ubm, R, seed=0):
+        """The starting point of EM -- OURS: T_cdr = 0.1 sqrt(var_cd) z, z standard normal drawn on the host by
+        ``numpy.random.default_rng(seed)`` in (C, D, R) order."""
+        R = int(R)
+        if not 1 <= R <= MAX_R:
+            raise ValueError("TotalVariability.from_ubm: R=%d must lie in [1, %d]" % (R, MAX_R))
+        z = np.random.default_rng(seed).standard_normal((ubm.C, ubm.D, R))
+        T = 0.1 * np.sqrt(ubm.var.cpu().numpy())[:, :, None] * z
+        return cls(torch.from_numpy(T).to(ubm.device), ubm.w, ubm.mu, ubm.var)
+
+    # ------------------------------------------------------------------ operations
+    def estep(self, N, Ft, want_M=False, w_out=None):
+        """One pass, no planning: ``Lp`` = N Pk and ``b`` = Ft G (``ssv_ivec_product``), then ``ssv_ivec_estep``.  Returns a namespace: ``w``
+        (U, R) float32, ``obj`` (U,) float64, ``M`` (U, P) float32 or None, and the device's own ``Lp`` (U, P), ``b`` (U, R)."""
+        N, Ft = _stats_pair(N, Ft, self.C, self.D, "TotalVariability.estep")
+        U, dev = N.shape[0], N.device
+        G, Pk = self.planes()
+        Lp, b = product(N, Pk), product(Ft, G)
+        w = w_out if w_out is not None else torch.empty((U, self.R), dtype=_F32, device=dev)
+        M = torch.empty((U, self.P), dtype=_F32, device=dev) if want_M else None
+        obj = torch.empty((U,), dtype=_F64, device=dev)
+        _lib.call("ssv_ivec_estep", _p(Lp), _p(b), _p(w), _p(M), _p(obj), U, self.R, ops._stream())
+        return SimpleNamespace(w=w, obj=obj, M=M, Lp=Lp, b=b)
+
+    def _passes(self, U, dev, train, who):
+        passes, need = plan_tv_passes(U, self.C, self.D, self.R, ops.free_bytes(dev), train)
+        ops.require_free_bytes(need, dev, "%s: %d utterances at C=%d, D=%d, R=%d need" % (who, U, self.C, self.D, self.R), "a smaller rank or UBM")
+        return passes
+
+    def em_step(self, N, Ft, min_div=True, min_count=10.0):
+        """One EM iteration over all utterances, in planned passes: per pass the E-step with M, then A += N^T M, Cm += Ft^T w, Nc += N^T 1
+        into float64 accumulators (``ssv_ivec_product_tn``) and sum M by ``ssv_gmm_stats_reduce``; then ``ssv_ivec_tv_update`` -- with
+        ``min_div`` after J = chol_lower(mean M), an R x R float64 factorisation on the host -- and the planes of the new ``T``.  Returns the
+        mean objective per utterance under the parameters BEFORE the update, a float64 device scalar."""
+        N, Ft = _stats_pair(N, Ft, self.C, self.D, "TotalVariability.em_step")
+        U, dev, C, D, R, P = N.shape[0], N.device, self.C, self.D, self.R, self.P
+        A = torch.zeros((C, P), dtype=_F64, device=dev)
+        Cm = torch.zeros((C * D, R), dtype=_F64, device=dev)
+        Nc = torch.zeros((C, 1), dtype=_F64, device=dev)
+        Msum = torch.zeros((P,), dtype=_F64, device=dev)
+        obj = torch.zeros((), dtype=_F64, device=dev)
+        for u0, u1 in self._passes(U, dev, True, "TotalVariability.em_step"):
+            e = self.estep(N[u0:u1], Ft[u0:u1], want_M=True)
+            product_tn(N[u0:u1], e.M, A)
+            product_tn(Ft[u0:u1], e.w, Cm)
+            product_tn(N[u0:u1], torch.ones((u1 - u0, 1), dtype=_F32, device=dev), Nc)
+            Msum += DiagUbm.reduce(e.M)
+            obj += e.obj.sum()
+        J = None
+        if min_div:
+            J = torch.from_numpy(np.linalg.cholesky(tri_unpack(Msum.cpu().numpy() / U, R))).to(dev).contiguous()
+        _lib.call("ssv_ivec_tv_update", _p(A), _p(Cm), _p(Nc), _p(J), _p(self.T), C, D, R, float(min_count), ops._stream())
+        self._planes = None
+        self.planes()
+        return obj / U
+
+    def fit(self, N, Ft, iters=5, min_div=True, min_count=10.0, log=print):
+        """``iters`` EM iterations (the recipe's --num-iters is 5); returns the history of mean objectives (each under the parameters its
+        iteration started from), host floats."""
+        hist = []
+        for it in range(int(iters)):
+            hist.append(float(self.em_step(N, Ft, min_div, min_count)))
+            if log:
+                log("ivector-extractor EM %d/%d: mean objective per utterance %.6f" % (it + 1, iters, hist[-1]))
+        return hist
+
+    def extract(self, N, Ft):
+        """The i-vectors ``w`` (U, R) float32 of resident statistics, in planned passes; every row is the bits of a one-pass E-step."""
+        N, Ft = _stats_pair(N, Ft, self.C, self.D, "TotalVariability.extract")
+        U, dev = N.shape[0], N.device
+        w = torch.empty((U, self.R), dtype=_F32, device=dev)
+        for u0, u1 in self._passes(U, dev, False, "TotalVariability.extract"):
+            self.estep(N[u0:u1], Ft[u0:u1], w_out=w[u0:u1])
+        return w
+
+
+def train_ivector_extractor(ubm, X, utt_off, R, iters=5, nsel=20, min_post=0.025, seed=0, min_div=True, min_count=10.0, log=print):
+    """Frames to a trained extractor: ``bw_stats``, ``centre_stats`` in place, ``TotalVariability.from_ubm(ubm, R, seed)`` and ``fit``.
+    Returns a namespace: ``tv``, ``history``, ``N`` (U, C), ``Ft`` (U, C, D)."""
+    N, F = bw_stats(ubm, X, utt_off, nsel, min_post)
+    Ft = centre_stats(ubm, N, F, out=F)
+    tv = TotalVariability.from_ubm(ubm, R, seed)
+    return SimpleNamespace(tv=tv, history=tv.fit(N, Ft, iters, min_div, min_count, log), N=N, Ft=Ft)
+
+
+def extract_ivectors(tv, X, utt_off, nsel=20, min_post=0.025):
+    """Frames to i-vectors (U, R) float32 under ``tv`` and its UBM, in passes planned by ``plan_extract_passes``: per pass the Baum-Welch
+    statistics of its utterances, centred in place, then the E-step; the statistics of all utterances are never resident at once.
+    ``utt_off``: a HOST sequence of U + 1 ascending offsets.  A row does not depend on the pass it went through."""
+    ubm = tv.ubm()
+    X = ubm._frames(X, "extract_ivectors")
+    if isinstance(utt_off, torch.Tensor):
+        utt_off = utt_off.cpu().numpy()
+    _, host = _offsets(np.asarray(utt_off), "extract_ivectors: utt_off", "cpu", total=X.shape[0])
+    U, C, D = host.size - 1, tv.C, tv.D
+    passes, need = plan_extract_passes(np.diff(host), C, D, tv.R, int(nsel), ops.free_bytes(X.device))
+    ops.require_free_bytes(need, X.device, "extract_ivectors: %d utterances at C=%d, D=%d, R=%d need" % (U, C, D, tv.R), "fewer utterances per call")
+    w = torch.empty((U, tv.R), dtype=_F32, device=X.device)
+    for u0, u1 in passes:
+        f0, f1 = int(host[u0]), int(host[u1])
+        if f1 == f0:
+            w[u0:u1].zero_()            # no frames: zero statistics, whose E-step is w = 0 exactly
+            continue
+        slab = ubm.stats(X[f0:f1], host[u0:u1 + 1] - f0, 1, nsel=nsel, min_post=min_post)
+        N, F = slab[:, :, 0].contiguous(), slab[:, :, 1:].contiguous()
+        tv.estep(N, centre_stats(tv, N, F, out=F), w_out=w[u0:u1])
+    return w
+
+
+# ------------------------------------------------------------------------------------------------------------ trials
+def cosine_trials(enroll, spk_off, evalv):
+    """``scores`` (E, S) float32: eval vector e against the model of speaker s, the re-normalised mean of the length-normalised enrolment
+    rows [spk_off[s], spk_off[s+1]) (``ssv_ivec_cosine_trials``).  A zero vector scores 0."""
+    enroll = _matrix(enroll, "cosine_trials: enroll")
+    evalv = _matrix(evalv, "cosine_trials: evalv", cols=enroll.shape[1])
+    off, host = _offsets(spk_off, "cosine_trials: spk_off", enroll.device, total=enroll.shape[0])
+    S = off.numel() - 1
+    scores = torch.empty((evalv.shape[0], S), dtype=_F32, device=enroll.device)
+    hp = None if host is None else host.ctypes.data_as(ctypes.c_void_p)
+    _lib.call("ssv_ivec_cosine_trials", _p(enroll), _p(off), hp, _p(evalv), _p(scores), enroll.shape[0], S, evalv.shape[0], enroll.shape[1], ops._stream())
+    return scores
+
+
+def _utt2spk(lines, who):
+    out = []
+    for line in lines:
+        line = line.rstrip("\r\t\n ")
+        parts = line.split(" ")
+        if len(parts) != 2:
+            raise ValueError("%s: %r is not '<utterance> <speaker>'" % (who, line))
+        out.append((parts[0], parts[1]))
+    return out
+
+
+def split_enroll_eval(utt2spk_lines, enroll_num=3):
+    """local/split_data_enroll_eval.py: per speaker, in the order speakers first appear, the first ``enroll_num`` utterances in file order
+    enrol and the rest are eval (the script's shuffle is commented out).  Returns (enroll_lines, eval_lines), '<utterance> <speaker>'."""
+    by_spk = {}
+    for utt, spk in _utt2spk(utt2spk_lines, "split_enroll_eval"):
+        by_spk.setdefault(spk, []).append(utt)
+    enroll, ev = [], []
+    for spk, utts in by_spk.items():
+        for i, utt in enumerate(utts):
+            (enroll if i < enroll_num else ev).append(utt + " " + spk)
+    return enroll, ev
+
+
+def trial_list(eval_utt2spk):
+    """local/produce_trials.py: every eval utterance, in file order, against every speaker of the file, in order of first appearance:
+    '<utterance> <speaker> target|nontarget'."""
+    pairs = _utt2spk(eval_utt2spk, "trial_list")
+    speakers = list(dict.fromkeys(spk for _, spk in pairs))
+    return ["%s %s %s" % (utt, target, "target" if target == spk else "nontarget") for utt, spk in pairs for target in speakers]
+
+
+def write_trial_scores(path, speakers, utterances, scores):
+    """The score file ``parse_ivector_scores`` reads: '<speaker> <utterance> <score>' per trial, utterance-major as ``trial_list`` orders
+    them; ``scores`` (len(utterances), len(speakers)), written with 9 significant digits (a float32 survives them)."""
+    scores = np.asarray(scores.detach().cpu() if isinstance(scores, torch.Tensor) else scores)
+    if scores.shape != (len(utterances), len(speakers)):
+        raise ValueError("write_trial_scores: scores are %s for %d utterances x %d speakers" % (scores.shape, len(utterances), len(speakers)))
+    with open(path, "w") as f:
+        for e, utt in enumerate(utterances):
+            for s, spk in enumerate(speakers):
+                f.write("%s %s %.9g\n" % (spk, utt, scores[e, s]))
