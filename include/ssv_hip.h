@@ -534,7 +534,7 @@ int ssv_gmm_diag_planes(const double* w, const double* mu, const double* var, fl
 /* ---- I-vector extractor: total-variability EM, extraction, cosine trials (additions; ABI version unchanged) ----
  * The middle of kaldi_ivectors/run.sh (extractor training, i-vector extraction, trial scores) on the Baum-Welch statistics above.  The
  * model is OURS, stated here; Kaldi's ivector-extractor-* binaries (prior offset, weight projection, full covariances) are NOT reproduced
- * and there is no PLDA: scoring is cosine on length-normalised vectors.  All arithmetic is independent of ssv_set_precision; no float
+ * (the back end is the next section; the trial entry here scores by cosine on length-normalised vectors).  All arithmetic is independent of ssv_set_precision; no float
  * atomics; the order of every sum follows from the shapes alone.  Bad arguments: -1; a shape beyond a kernel: -2; both before any launch.
  * Limits of every entry that takes them: 1 <= R <= 192 (the packed float64 triangle of R = 192, 148,224 bytes, is the most one
  * workgroup's LDS holds), C <= 2048, D <= 128.
@@ -581,6 +581,77 @@ int ssv_ivec_tv_update(const double* A, const double* Cm, const double* Nc, cons
  * scores 0, never NaN.  S R 4 bytes beyond 128 KiB of LDS: -2. */
 int ssv_ivec_cosine_trials(const float* enroll, const long* spk_off, const long* spk_off_host, const float* evalv, float* scores, long n_enroll, int S,
                            long E, int R, ssv_stream_t stream);
+
+/* ---- I-vector back end: PLDA (additions; ABI version unchanged) ----
+ * The last third of kaldi_ivectors/run.sh (ivector-compute-plda, ivector-plda-scoring --num-utts; compute-eer is host arithmetic in
+ * spoofsv_amd/plda.py).  The model is OURS, stated here; Kaldi's binaries are NOT reproduced bit for bit.  1 <= R <= 192 as for the
+ * extractor (R < 1: -1, R > 192: -2).  All arithmetic is independent of ssv_set_precision; no float atomics; the order of every sum follows
+ * from the shapes alone.  Bad arguments: -1; a shape beyond a kernel: -2; both before any launch.  P = R (R + 1) / 2, packed as above.
+ *
+ * The model is two-covariance PLDA: x = mu + y_s + e, y_s ~ N(0, B) per speaker, e ~ N(0, W) per utterance.
+ * Length normalisation: xh = x sqrt(R) / |x|; a zero vector stays zero.
+ * Statistics: per speaker k with n_k >= 1 rows the mean m_k in double; the residual rows d_i = xh_i - m_s(i), rounded once to float32; the
+ *   scatter Sigma = sum_i d_i d_i^T, taken on the residuals so that nothing cancels; mu = the unweighted mean over speakers of m_k.  Speakers
+ *   without rows are left out of everything.
+ * EM, from W = B = I, all in float64; per iteration, for every distinct count n among the speakers Mx_n = (B^-1 + n W^-1)^-1, then per speaker
+ *   w_k = n_k Mx W^-1 (m_k - mu) and r_k = (m_k - mu) - w_k, and
+ *   B <- (1/S) sum_k (Mx_{n_k} + w_k w_k^T),   W <- (Sigma + sum_k n_k (Mx_{n_k} + r_k r_k^T)) / N   (S speakers with rows, N rows).
+ * Objective (the data's marginal log-likelihood up to a constant; EM may not decrease it):
+ *   obj = (1/N) { -1/2 [(N - S) log|W| + tr(W^-1 Sigma)] - 1/2 sum_k [log|B + W/n_k| + (m_k - mu)^T (B + W/n_k)^-1 (m_k - mu)] }.
+ * Finalise (host, float64, once per model): W = C C^T, C^-1 B C^-T = U diag(psi) U^T with psi floored at 0 and descending, A = U^T C^-1, each
+ *   row's sign fixed so that its entry of largest magnitude is positive.  The model is (mu, A, psi).
+ * Transform: u = A (xh - mu), then u <- u sqrt(R / sum_d u_d^2 / (psi_d + 1/n)), n the number of utterances behind the vector; the factor is
+ *   1 where that sum is 0.
+ * Speaker model: each enrolment row normalised, their mean, normalised again, transformed with n = the number of its rows.  Eval vectors are
+ *   normalised and transformed with n = 1.
+ * Score: c = n psi / (n psi + 1), v = 1 + psi / (n psi + 1), a = 1 / v,
+ *   LLR(t | y, n) = -1/2 sum_d [log v_d + a_d (t_d - c_d y_d)^2] + 1/2 sum_d [log(psi_d + 1) + t_d^2 / (psi_d + 1)];  n = 0 scores exactly 0.
+ *
+ * ssv_plda_class_stats: X (n, R) float32; spk_off (S + 1) int64 DEVICE, speaker k owning rows [spk_off[k], spk_off[k+1]) (spk_off_host: the same
+ * table as a HOST array or NULL; when given, checked here -- ascending, inside [0, n], else -1; the device clamps what it reads and takes a
+ * descending pair as empty).  A workgroup per speaker: with length_norm != 0 each row's factor sqrt(R / |x|^2) in double, the mean in double
+ * over the rows in ascending order.  Outputs, each optional (at least one): Xd (n, R) float32 the residual rows; means (S, R) float64; mu (R)
+ * float64 (needs means); model (S, R) float32 = m_k sqrt(R) / |m_k| rounded once -- the speaker model before its transform.  A speaker without
+ * rows leaves its rows of Xd and means untouched and gets a zero model row. */
+int ssv_plda_class_stats(const float* X, const long* spk_off, const long* spk_off_host, float* Xd, double* means, double* mu, float* model, long n, int S,
+                         int R, int length_norm, ssv_stream_t stream);
+/* out_j (P) = (a + coef_j b_j)^-1, j < J, and when logdet is not NULL logdet_j = log|a + coef_j b_j|.  a (P) packed float64; b_j = b + j
+ * b_stride, packed float64 (b_stride = 0: one b for all; b_stride >= P: J matrices); a == NULL: the inverse of coef_j b_j; coef (J) float64
+ * DEVICE, NULL: ones (with a == NULL, J = 2 and b_stride = P two plain inverses, which serves W^-1 and B^-1 in one launch).  A workgroup
+ * per matrix, the triangle in LDS (153,856 bytes at R = 192), by the extractor's Cholesky, trtri and lauum.  A pivot that is not
+ * positive (a NaN among the inputs included) gives NaN in out_j and logdet_j and touches nothing else. */
+int ssv_plda_mixed_inverse(const double* a, const double* b, long b_stride, const double* coef, double* out, double* logdet, int J, int R, ssv_stream_t stream);
+/* The E-step, a workgroup per speaker, float64: with n = cnt[k] and Mx_{cls[k]} (Mx (J, P), the mixed inverses of B^-1 + n W^-1),
+ * c = means_k - mu, t = Winv c, w_k = n Mx t, r_k = c - w_k and quad_k = n t . r_k, which is c^T (B + W/n)^-1 c by the matrix inversion
+ * lemma.  cnt, cls (S) int32 DEVICE.  cnt[k] <= 0 (or cls[k] outside [0, J)): w_k = r_k = 0, quad_k = 0.  w, r (S, R), quad (S) float64. */
+int ssv_plda_em_classes(const double* means, const double* mu, const int* cnt, const int* cls, const double* Mx, const double* Winv, double* w, double* r,
+                        double* quad, int S, int J, int R, ssv_stream_t stream);
+/* acc (R, R) float64 += V^T diag(c) V, V (S, R), c (S) float64 (NULL: ones).  Each element has one owner, which adds the rows in ascending
+ * order. */
+int ssv_plda_wsyrk_f64(const double* V, const double* c, double* acc, long S, int R, ssv_stream_t stream);
+/* The M-step and the objective.  Per class j < J of equal counts: nspk_j speakers, nrow_j = nspk_j n_j rows (float64), Mx_j, ldMx_j =
+ * log|B^-1 + n_j W^-1| (the logdet of ssv_plda_mixed_inverse).  WW = sum w w^T, RR = sum n r r^T, Sigma: (R, R) float64.  With W, B (P, packed)
+ * not NULL:  B = (sum_j nspk_j Mx_j + WW) / Sn,  W = (Sigma + sum_j nrow_j Mx_j + RR) / N.  With obj (1) not NULL the objective above UNDER THE
+ * PARAMETERS THE INPUTS WERE TAKEN FROM, where log|B + W/n| = ldW - R log n + ldB + ldMx and the quadratic forms are quad; ldW, ldB (1)
+ * float64 DEVICE.  Sn: the speakers with rows, N: the rows.  W, B must not be the arrays Winv was computed into. */
+int ssv_plda_em_update(const double* Mx, const double* ldMx, const double* nspk, const double* nrow, const double* WW, const double* RR, const double* Sigma,
+                       const double* Winv, const double* ldW, const double* ldB, const int* cnt, const int* cls, const double* quad, double* W, double* B,
+                       double* obj, int J, int S, int R, double Sn, double N, ssv_stream_t stream);
+/* U (n, R) float32 = the transform of X (n, R): Xc = x f - mu, one float32 fused multiply-add per element BEFORE the product (f = sqrt(R /
+ * |x|^2) rounded once, 1 with length_norm == 0; mu rounded once), then the product Xc At of ssv_ivec_product -- At (R, R) float32 = A^T, rounded
+ * once from double by the caller -- then per row, a wave each, the sum over d of u_d^2 / (psi_d + 1/n) in double and the scaling, rounded
+ * once.  n = nex[row] (int32 DEVICE) or, with nex == NULL, nex_all.  Xc (n, R): a workspace, distinct from X and U. */
+int ssv_plda_transform(const float* X, const double* mu, const float* At, const double* psi, const int* nex, int nex_all, float* Xc, float* U, long n, int R,
+                       int length_norm, ssv_stream_t stream);
+/* The score's right operand, a workgroup per speaker, formed in double: H (S, 2 R) float32 = [-1/2 (a - 1/(psi + 1)), a c y] rounded once,
+ * k (S) float64 = -1/2 sum a c^2 y^2 - 1/2 sum (log v - log(psi + 1)).  y (S, R) float32 the transformed speaker models, nspk (S) int32
+ * DEVICE their row counts; nspk[s] <= 0: H_s and k_s are exactly zero. */
+int ssv_plda_speaker_planes(const float* y, const int* nspk, const double* psi, float* H, double* k, int S, int R, ssv_stream_t stream);
+/* scores (E, S) float32 = [t^2, t] H^T + k in one launch, T (E, R) float32 the transformed eval vectors: a workgroup owns a 64 x 64 tile;
+ * the left operand is formed from the eval tile as it is staged (t^2 one float32 product), so no (E, 2 R) array exists; the product runs on
+ * v_mfma_f32_16x16x4_f32 in fp32 chains of at most 256 elements of K = 2 R <= 384, added in double registers; k_s is added in double and the
+ * result rounded once.  A row of the output does not depend on the rows that share its launch.  More than 65535 x 64 rows: -2. */
+int ssv_plda_score(const float* T, const float* H, const double* k, float* scores, long E, long S, int R, ssv_stream_t stream);
 
 /* ---- Vocoder and spectrogram front end ------------------------------------------------
  * Replaces the CPU tail of synthesis, synthesize.py:138-147 / generate_test_utterances.py:128-139

@@ -599,12 +599,15 @@ def ivector_curve(score_file, enroll_utt_num=3, eval_utt_num=20, thresholds=None
     return dict(thresholds=thresholds, spoof_rate=counts[:, 1].astype(np.int64) / L, gt_frr=1 - counts[:, 0].astype(np.int64) / L, counts=counts)
 
 
-def ivector_trials(enroll, enroll_utt2spk, evalv, eval_utt2spk, score_file, thresholds, enroll_utt_num=3, eval_utt_num=20):
+def ivector_trials(enroll, enroll_utt2spk, evalv, eval_utt2spk, score_file, thresholds=None, enroll_utt_num=3, eval_utt_num=20, plda=None):
     """The trials of the i-vector system without Kaldi: ``enroll`` (n, R) and ``evalv`` (E, R) float32 device i-vectors with their
     '<utterance> <speaker>' lines (``ivector.split_enroll_eval`` order: a speaker's enrolment rows are consecutive), scored by cosine on the
     device (``ivector.cosine_trials``), written to ``score_file`` in ``trial_list`` order as '<speaker> <utterance> <score>', and swept by
     ``ivector_curve(score_file, thresholds=thresholds)``, whose dict is returned with ``scores`` (E, S) and ``speakers`` added.
-    ``thresholds`` is required: ``curve_thresholds("ivector")`` spans PLDA's range, cosine scores lie in [-1, 1]."""
+    Without ``plda`` the ``thresholds`` are required: ``curve_thresholds("ivector")`` spans PLDA's range, cosine scores lie in [-1, 1].
+    ``plda``: a ``plda.Plda`` model; the scores are then its log-likelihood ratios (``Plda.trials``), ``thresholds=None`` means
+    ``curve_thresholds("ivector")``, and the dict gains ``eer`` and ``eer_threshold``: ``plda.compute_eer`` over the target / nontarget
+    trials of ``ivector.trial_list``."""
     from . import ivector
     en, ev = ivector._utt2spk(enroll_utt2spk, "ivector_trials"), ivector._utt2spk(eval_utt2spk, "ivector_trials")
     if len(en) != enroll.shape[0] or len(ev) != evalv.shape[0]:
@@ -618,11 +621,36 @@ def ivector_trials(enroll, enroll_utt2spk, evalv, eval_utt2spk, score_file, thre
                 off.append(i)
             speakers.append(spk)
     off.append(len(en))
-    scores = ivector.cosine_trials(enroll, off, evalv)
+    if plda is None and thresholds is None:
+        raise TypeError("ivector_trials: thresholds are required for cosine scores (curve_thresholds('ivector') spans PLDA's range)")
+    scores = ivector.cosine_trials(enroll, off, evalv) if plda is None else plda.trials(enroll, off, evalv)
     ivector.write_trial_scores(score_file, speakers, [utt for utt, _ in ev], scores)
     out = ivector_curve(score_file, enroll_utt_num, eval_utt_num, thresholds, device=enroll.device)
     out.update(scores=scores, speakers=speakers)
+    if plda is not None:
+        from .plda import compute_eer
+        target = np.array([[spk == model for model in speakers] for _, spk in ev], dtype=bool)         # trial_list's labels, as a mask
+        host = scores.cpu().numpy()
+        out["eer"], out["eer_threshold"] = compute_eer(host[target], host[~target])
     return out
+
+
+def ivector_eer(score_file, trial_lines):
+    """The last line of kaldi_ivectors/ivector_eer.sh -- awk '{print $3}' scores | paste - trials | awk '{print $1, $4}' | compute-eer -- the
+    third column of line i of the score file paired with the target / nontarget label of line i of ``trial_lines`` ('<utterance> <speaker>
+    target|nontarget', ``ivector.trial_list``), then ``plda.compute_eer``.  Returns (eer, threshold)."""
+    from .plda import compute_eer
+    with open(score_file, "r") as f:
+        scores = [line.split() for line in f if line.strip()]
+    trials = [line.split() for line in trial_lines if line.strip()]
+    if len(scores) != len(trials):
+        raise ValueError("ivector_eer: %d score lines for %d trials" % (len(scores), len(trials)))
+    groups = {"target": [], "nontarget": []}
+    for sc, tr in zip(scores, trials):
+        if len(sc) != 3 or len(tr) != 3 or tr[2] not in groups:
+            raise ValueError("ivector_eer: %r / %r are not '<speaker> <utterance> <score>' and '<utterance> <speaker> target|nontarget'" % (" ".join(sc), " ".join(tr)))
+        groups[tr[2]].append(float(sc[2]))
+    return compute_eer(groups["target"], groups["nontarget"])
 
 
 def ivector_spoofrate(score_file, thres, train_spk_num=88, enroll_utt_num=3, eval_utt_num=20, device="cuda"):

@@ -8,8 +8,8 @@ restatement (``tests/_ivector_ref.py``) is the yardstick.  Ours, not Kaldi's: th
 treatment of a starved Gaussian in the M-step.
 
 The extractor (``TotalVariability``) is this project's model too, stated at the entries of ``include/ssv_hip.h`` ("I-vector extractor"):
-no prior offset, no weight projection, no full covariances, no PLDA -- scoring is cosine on length-normalised vectors -- and its yardstick
-is ``tests/_ivector_tv_ref.py``.
+no prior offset, no weight projection, no full covariances; scoring here is cosine on length-normalised vectors (PLDA is ``plda.py``) -- and its
+yardstick is ``tests/_ivector_tv_ref.py``.
 
 Every FLOP of the hot path runs in ``csrc/ivector.hip`` and ``csrc/ivector_tv.hip``; torch is plumbing (memory, the stream).  Tensors must
 live on a ROCm device.
