@@ -531,6 +531,67 @@ int ssv_gmm_diag_update(const double* stats, double* w, double* mu, double* var,
                         double min_count, double min_weight, ssv_stream_t stream);
 int ssv_gmm_diag_planes(const double* w, const double* mu, const double* var, float* A, float* B, float* g, int C, int D, ssv_stream_t stream);
 
+/* ---- I-vector groundwork: full-covariance UBM (additions; ABI version unchanged) ----
+ * The second link of kaldi_ivectors/run.sh (sid/train_full_ubm.sh), between the diagonal UBM above and the extractor below.  The model is
+ * OURS, stated here; Kaldi's fgmm-global-* binaries (eigenvalue flooring, Gaussian removal) are NOT reproduced.  All arithmetic is
+ * independent of ssv_set_precision; no float atomics; the order of every sum follows from the shapes and the selection lists alone, so
+ * the same inputs give the same bits.  Limits: 1 <= D <= 128, 1 <= C <= 2048, 1 <= nsel <= 32, F nsel < 2^31.  Bad arguments: -1; beyond
+ * the limits: -2; both before any launch.
+ *
+ * Mixture: w (C), mu (C, D), cov (C, Pd) float64, Pd = D (D + 1) / 2, cov_c the PACKED lower triangle of Sigma_c, row-major (element
+ * (i, j), j <= i, at i (i + 1) / 2 + j).  Sigma_c = L_c L_c^T (Cholesky), W_c = L_c^-1 (lower triangular).  The log-likelihood is taken
+ * in the centred, whitened form, in which nothing cancels:
+ *   z = W_c (x - mu_c),   L_fc = g_c - 1/2 |z|^2,   g_c = log w_c - 1/2 (D log 2 pi + log|Sigma_c|),
+ * x - mu_c being ONE float32 subtraction on mu rounded once, before any product.  Planes: Wt (C, D, D) float32, Wt[c][i][j] = W_c (i, j),
+ * exact zeros above the diagonal; muf (C, D) and g (C) float32; each rounded once from double; icov (C, Pd) float64 = packed Sigma_c^-1
+ * (for ssv_ivec_tv_planes_full).
+ *
+ * ssv_fgmm_planes: a workgroup per Gaussian, float64, the packed triangle in LDS: Cholesky, the triangular inverse, W^T W (LAPACK's
+ * potrf / trtri / lauum forms, as ssv_ivec_estep), log|Sigma| from the pivots.  A pivot that is not positive: that Gaussian's Wt, muf,
+ * g and icov are NaN and nothing else is touched. */
+int ssv_fgmm_planes(const double* w, const double* mu, const double* cov, float* Wt, float* muf, float* g, double* icov, int C, int D,
+                    ssv_stream_t stream);
+/* The Gaussian-major selection lists of idx (F, nsel) int32 as ssv_gmm_diag_gselect writes it.  Slot f * nsel + j belongs to the list of
+ * Gaussian idx[f][j]; start (C + 1) int32 and pairs (F nsel) int32 OUT: pairs[start[c] : start[c + 1]] = the slots of c in ASCENDING slot
+ * order (a stable counting sort on the device; integer counts, and no position depends on the order in which anything ran).  An idx
+ * outside [0, C) belongs to no list; pairs beyond start[C] are not written.  ws: ssv_fgmm_group_workspace bytes.
+ * ssv_fgmm_pair_tile: pairs of a list one workgroup of the two product entries below owns per step (tests put list lengths on its edges).
+ * A list is split into runs of whole tiles, ssv_fgmm_stats_runs(F, nsel, C) of them for the statistics: the count follows from the shapes
+ * alone and a run's extent from the list's length alone.  The *_workspace queries return bytes, 0 for arguments the entries refuse. */
+int ssv_fgmm_pair_tile(void);
+int ssv_fgmm_stats_runs(long F, int nsel, int C);
+long ssv_fgmm_group_workspace(long F, int nsel, int C);
+long ssv_fgmm_post_workspace(long F, int nsel);
+long ssv_fgmm_stats_workspace(long F, int nsel, int C, int D);
+int ssv_fgmm_group_selection(const int* idx, int* start, int* pairs, long F, int nsel, int C, void* ws, size_t ws_bytes, ssv_stream_t stream);
+/* Posteriors over a given selection.  A workgroup owns (Gaussian c, run of its list): Wt_c is staged in LDS once and serves every pair of
+ * the run; per tile the pairs' frame rows are gathered into LDS and centred on muf_c, Z = Xc Wt_c^T runs on v_mfma_f32_16x16x4_f32 (K = D:
+ * the fp32 rate does not limit it), |z|^2 is added along the row and L is written per slot.  A frame-major finish then takes, over the
+ * frame's slots in idx's order: loglik (F) = log-sum-exp of L, post (F, nsel) = the soft max, entries below min_post set to 0 (never the
+ * first largest) and the rest renormalised.  A slot whose idx lies outside [0, C) has posterior 0 and takes no part; a frame with no slot
+ * inside has posteriors 0 and loglik -inf.  A frame's post and loglik do not depend on the other frames of the call: a row of the product
+ * depends on its own K chain only.  ws: ssv_fgmm_post_workspace bytes (L per slot). */
+int ssv_fgmm_select_post(const float* X, const float* Wt, const float* muf, const float* g, const int* idx, const int* start, const int* pairs,
+                         float* post, float* loglik, long F, int D, int C, int nsel, float min_post, void* ws, size_t ws_bytes, ssv_stream_t stream);
+/* Statistics centred on the CURRENT mean, over each Gaussian's list: out (C, 1 + D + Pd) float64 = [N_c, S1_c, S2_c],
+ *   N_c = sum gamma,   S1_c = sum gamma (x - mu_c),   S2_c = sum gamma (x - mu_c)(x - mu_c)^T (packed),   gamma = post[slot],
+ * x - mu_c as above (muf).  Centring on the old mean is what keeps the M-step's Sigma = S2 / N - delta delta^T from cancelling.  Per tile
+ * of 64 pairs S2 = (gamma Xc)^T Xc runs on the fp32 MFMA (K = the 64 pairs in list order) and S1, N are fp32 chains over the same pairs;
+ * the tiles are added in double along the run, the run's sums rounded once to float32 into ws and the runs added in ascending order in
+ * double (ssv_gmm_stats_reduce's kernel).  A pair of posterior 0 (pruned) is MULTIPLIED by its zero, not skipped.  An empty list gives
+ * exact zeros.  ws: ssv_fgmm_stats_workspace bytes. */
+int ssv_fgmm_stats(const float* X, const float* muf, const float* post, const int* start, const int* pairs, double* out, long F, int D, int C,
+                   int nsel, void* ws, size_t ws_bytes, ssv_stream_t stream);
+/* M-step, a workgroup per Gaussian plus one launch for the weights, all in float64.  stats as ssv_fgmm_stats writes them;
+ * w (C) OUT, mu (C, D) and cov (C, Pd) IN / OUT, kept (C) int32 OUT:
+ *   delta = S1 / N;   mu <- mu + delta;   Sigma <- S2 / N - delta delta^T.
+ * A Gaussian KEEPS its mu and cov bit for bit and has kept[c] = 1 when N_c < min_count (or N_c <= 0), or when the new Sigma has a
+ * Cholesky pivot L_ii^2 < var_floor (or not positive) -- L_ii^2 is the conditional variance of dimension i given the dimensions before
+ * it.  (The project's own rule: Kaldi floors eigenvalues and removes Gaussians.)  w_c = N_c / sum N, a kept Gaussian taking
+ * max(w_c, min_weight), then renormalised to sum 1 (ssv_gmm_diag_update's rule).  Wt, muf, g, icov OUT: the planes of the result. */
+int ssv_fgmm_update(const double* stats, double* w, double* mu, double* cov, float* Wt, float* muf, float* g, double* icov, int* kept, int C,
+                    int D, double var_floor, double min_count, double min_weight, ssv_stream_t stream);
+
 /* ---- I-vector extractor: total-variability EM, extraction, cosine trials (additions; ABI version unchanged) ----
  * The middle of kaldi_ivectors/run.sh (extractor training, i-vector extraction, trial scores) on the Baum-Welch statistics above.  The
  * model is OURS, stated here; Kaldi's ivector-extractor-* binaries (prior offset, weight projection, full covariances) are NOT reproduced
@@ -547,6 +608,10 @@ int ssv_gmm_diag_planes(const double* w, const double* mu, const double* var, fl
  * ssv_ivec_centre_stats: Ft (U, C, D) = F - N mu, one float32 fused multiply-add per element (mu rounded once); Ft may be F. */
 int ssv_ivec_tv_planes(const double* T, const double* var, float* G, float* Pk, int C, int D, int R, ssv_stream_t stream);
 int ssv_ivec_centre_stats(const float* N, const float* F, const double* mu, float* Ft, long U, int C, int D, ssv_stream_t stream);
+/* The same planes on a full-covariance UBM: icov (C, Pd) float64 = packed Sigma_c^-1 as ssv_fgmm_planes / ssv_fgmm_update write it;
+ * G_c = Sigma_c^-1 T_c and Pk_c = packed T_c^T G_c, summed over d in double (ascending) and rounded once; outputs and layout as
+ * ssv_ivec_tv_planes, and nothing below the planes knows the difference.  R < 1: -1; R > 192, C > 2048 or D > 128: -2. */
+int ssv_ivec_tv_planes_full(const double* T, const double* icov, float* G, float* Pk, int C, int D, int R, ssv_stream_t stream);
 /* The product family, on v_mfma_f32_16x16x4_f32 (exact fp32 fma chains), all operands row-major:
  *   ssv_ivec_product:     out (m, n) float32 = A (m, K) B (K, n), rounded once;
  *   ssv_ivec_product_tn:  acc (m, n) float64 += A (U, m)^T B (U, n)  (K = U; acc persists across the passes of an accumulation).

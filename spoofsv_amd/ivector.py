@@ -2,17 +2,17 @@
 and first order, per utterance), the total-variability extractor trained by EM on them, i-vector extraction and cosine trial scores.
 
 This is the bottom of the reference's ``kaldi_ivectors/run.sh`` (MFCC -> VAD -> diagonal UBM -> full UBM -> extractor -> PLDA), as far
-as the diagonal UBM.  Kaldi's binaries are NOT reproduced: its MFCC (povey window, snip-edges, energy in C0), its energy VAD and the
-recipe's ``conf/`` values are not pinned here; the algorithms are the ones stated at the entries in ``include/ssv_hip.h``, and a float64
-restatement (``tests/_ivector_ref.py``) is the yardstick.  Ours, not Kaldi's: the initialisation of ``DiagUbm.from_frames`` and the
-treatment of a starved Gaussian in the M-step.
+as the full-covariance UBM (``FullUbm``, ``train_full_ubm``; yardstick ``tests/_fgmm_ref.py``).  Kaldi's binaries are NOT reproduced: its
+MFCC (povey window, snip-edges, energy in C0), its energy VAD and the recipe's ``conf/`` values are not pinned here; the algorithms are
+the ones stated at the entries in ``include/ssv_hip.h``, and a float64 restatement (``tests/_ivector_ref.py``) is the yardstick.  Ours,
+not Kaldi's: the initialisation of ``DiagUbm.from_frames`` and the treatment of a starved or degenerate Gaussian in the M-steps.
 
 The extractor (``TotalVariability``) is this project's model too, stated at the entries of ``include/ssv_hip.h`` ("I-vector extractor"):
-no prior offset, no weight projection, no full covariances; scoring here is cosine on length-normalised vectors (PLDA is ``plda.py``) -- and its
-yardstick is ``tests/_ivector_tv_ref.py``.
+no prior offset, no weight projection; the UBM under it is diagonal (``DiagUbm``) or full-covariance (``FullUbm``); scoring here is
+cosine on length-normalised vectors (PLDA is ``plda.py``) -- and its yardstick is ``tests/_ivector_tv_ref.py``.
 
-Every FLOP of the hot path runs in ``csrc/ivector.hip`` and ``csrc/ivector_tv.hip``; torch is plumbing (memory, the stream).  Tensors must
-live on a ROCm device.
+Every FLOP of the hot path runs in ``csrc/ivector.hip``, ``csrc/fgmm.hip`` and ``csrc/ivector_tv.hip``; torch is plumbing (memory, the
+stream).  Tensors must live on a ROCm device.
 """
 import ctypes
 from types import SimpleNamespace
@@ -257,6 +257,221 @@ class DiagUbm:
         return hist
 
 
+class FullUbm:
+    """A full-covariance Gaussian mixture on one device (``include/ssv_hip.h``, "full-covariance UBM"): ``w`` (C,), ``mu`` (C, D) and
+    ``cov`` (C, Pd) float64, ``cov`` the packed lower triangles of the covariances (``tri_pack``), with the planes the kernels read:
+    the float32 whitening matrices ``Wt`` (C, D, D), ``muf`` (C, D), ``g`` (C,) and the float64 packed inverses ``icov`` (C, Pd).
+    The Gaussians of a frame are selected by the diagonal mixture ``self.diag()``; the posteriors over the selected are the full ones."""
+
+    def __init__(self, w, mu, cov):
+        for t, name in ((w, "w"), (mu, "mu"), (cov, "cov")):
+            if not isinstance(t, torch.Tensor):
+                raise ValueError("FullUbm: %s must be a torch tensor" % name)
+        if mu.dim() != 2 or cov.dim() != 2 or cov.shape != (mu.shape[0], tri_size(mu.shape[1])) or w.shape != (mu.shape[0],) \
+                or any(t.dtype != _F64 for t in (w, mu, cov)):
+            raise ValueError("FullUbm: need float64 w (C,), mu (C, D), cov (C, D (D + 1) / 2); got %s %s, %s %s, %s %s"
+                             % (w.dtype, tuple(w.shape), mu.dtype, tuple(mu.shape), cov.dtype, tuple(cov.shape)))
+        C, D = mu.shape
+        if not (1 <= C <= MAX_C and 1 <= D <= MAX_D):
+            raise ValueError("FullUbm: C=%d must lie in [1, %d] and D=%d in [1, %d]" % (C, MAX_C, D, MAX_D))
+        if w.device != mu.device or cov.device != mu.device:
+            raise ValueError("FullUbm: w, mu and cov must live on one device")
+        self.w, self.mu, self.cov = w.contiguous().clone(), mu.contiguous().clone(), cov.contiguous().clone()
+        self._planes = self._diag = None
+
+    C = property(lambda self: self.mu.shape[0])
+    D = property(lambda self: self.mu.shape[1])
+    Pd = property(lambda self: self.cov.shape[1])
+    device = property(lambda self: self.mu.device)
+
+    def _alloc_planes(self):
+        C, D, dev = self.C, self.D, self.device
+        return (torch.empty((C, D, D), dtype=_F32, device=dev), torch.empty((C, D), dtype=_F32, device=dev), torch.empty((C,), dtype=_F32, device=dev),
+                torch.empty((C, self.Pd), dtype=_F64, device=dev))
+
+    def planes(self):
+        """(Wt, muf, g, icov) of the current parameters: built on the device at first use (``ssv_fgmm_planes``), rewritten by every
+        M-step.  The state itself may sit on the host; every operation needs a ROCm device."""
+        if self._planes is None:
+            for t, name in ((self.w, "w"), (self.mu, "mu"), (self.cov, "cov")):
+                ops._dev(t, "FullUbm: " + name)
+            pl = self._alloc_planes()
+            _lib.call("ssv_fgmm_planes", _p(self.w), _p(self.mu), _p(self.cov), *(_p(t) for t in pl), self.C, self.D, ops._stream())
+            self._planes = pl
+        return self._planes
+
+    Wt = property(lambda self: self.planes()[0])
+    muf = property(lambda self: self.planes()[1])
+    g = property(lambda self: self.planes()[2])
+    icov = property(lambda self: self.planes()[3])
+
+    @property
+    def var(self):
+        """diag(Sigma) (C, D) float64."""
+        i = torch.arange(self.D, device=self.device)
+        return self.cov[:, i * (i + 1) // 2 + i].contiguous()
+
+    @classmethod
+    def from_diag(cls, diag_ubm):
+        """The full mixture whose covariances are ``diag_ubm``'s diagonals: where ``sid/train_full_ubm.sh`` starts."""
+        C, D = diag_ubm.mu.shape
+        cov = torch.zeros((C, tri_size(D)), dtype=_F64, device=diag_ubm.device)
+        i = torch.arange(D, device=diag_ubm.device)
+        cov[:, i * (i + 1) // 2 + i] = diag_ubm.var
+        return cls(diag_ubm.w, diag_ubm.mu, cov)
+
+    def diag(self):
+        """The selector: a ``DiagUbm`` on diag(Sigma), rebuilt after every update."""
+        if self._diag is None:
+            self._diag = DiagUbm(self.w, self.mu, self.var)
+        return self._diag
+
+    # ------------------------------------------------------------------ state
+    def state_dict(self):
+        return {"w": self.w.clone(), "mu": self.mu.clone(), "cov": self.cov.clone()}
+
+    def load_state_dict(self, sd):
+        new = FullUbm(sd["w"].to(self.device), sd["mu"].to(self.device), sd["cov"].to(self.device))
+        self.__dict__.update(new.__dict__)
+        return self
+
+    def save(self, path):
+        """``.npz`` with the float64 ``w``, ``mu``, ``cov`` (the planes are derived)."""
+        np.savez(path, w=self.w.cpu().numpy(), mu=self.mu.cpu().numpy(), cov=self.cov.cpu().numpy())
+
+    @classmethod
+    def load(cls, path, device="cuda"):
+        """``device="cpu"`` gives a state holder only (to inspect or move); the operations need a ROCm device."""
+        with np.load(path) as z:
+            return cls(*(torch.from_numpy(np.asarray(z[k], dtype=np.float64)).to(device) for k in ("w", "mu", "cov")))
+
+    # ------------------------------------------------------------------ operations
+    def _frames(self, X, who):
+        return _matrix(X, who + ": X", cols=self.D)
+
+    def _idx(self, idx, F, who):
+        idx = _matrix(idx, who + ": idx", dtype=_I32)
+        if idx.shape[0] != F or idx.shape[1] > MAX_NSEL:
+            raise ValueError("%s: idx must be (%d, nsel <= %d), got %s" % (who, F, MAX_NSEL, tuple(idx.shape)))
+        return idx
+
+    def group(self, idx):
+        """The Gaussian-major lists of a selection ``idx`` (F, nsel) int32 (``ssv_fgmm_group_selection``): ``(start (C + 1,), pairs
+        (F nsel,))`` int32, ``pairs[start[c]:start[c + 1]]`` the slots f * nsel + j whose Gaussian is c, ascending."""
+        idx = _matrix(idx, "FullUbm.group: idx", dtype=_I32)
+        F, nsel = idx.shape
+        if nsel > MAX_NSEL:
+            raise ValueError("FullUbm.group: idx has %d columns, at most %d" % (nsel, MAX_NSEL))
+        start = torch.empty((self.C + 1,), dtype=_I32, device=idx.device)
+        pairs = torch.empty((F * nsel,), dtype=_I32, device=idx.device)
+        nws = _lib.query("ssv_fgmm_group_workspace", F, nsel, self.C)
+        ws = ops._ws(nws, idx.device)
+        _lib.call("ssv_fgmm_group_selection", _p(idx), _p(start), _p(pairs), F, nsel, self.C, _p(ws), ws.numel(), ops._stream())
+        return start, pairs
+
+    def posteriors(self, X, nsel=20, min_post=0.0, idx=None, groups=None, loglik_out=None):
+        """``idx`` (F, nsel) int32 -- given, or the ``nsel`` likeliest Gaussians of ``self.diag()`` -- with the FULL-covariance posteriors
+        among them (those below ``min_post`` zeroed, the rest renormalised) and the log-likelihood over the selected:
+        ``(idx, post (F, nsel), loglik (F,))``.  ``groups``: ``self.group(idx)`` when the caller holds it already."""
+        X = self._frames(X, "FullUbm.posteriors")
+        F = X.shape[0]
+        if not 0.0 <= min_post < 1.0:
+            raise ValueError("FullUbm.posteriors: min_post=%r must lie in [0, 1)" % (min_post,))
+        if idx is None:
+            idx = self.diag().posteriors(X, nsel, 0.0)[0]
+            groups = None
+        idx = self._idx(idx, F, "FullUbm.posteriors")
+        start, pairs = groups if groups is not None else self.group(idx)
+        nsel = idx.shape[1]
+        post = torch.empty((F, nsel), dtype=_F32, device=X.device)
+        ll = loglik_out if loglik_out is not None else torch.empty((F,), dtype=_F32, device=X.device)
+        nws = _lib.query("ssv_fgmm_post_workspace", F, nsel)
+        ws = ops._ws(nws, X.device)
+        Wt, muf, g, _ = self.planes()
+        _lib.call("ssv_fgmm_select_post", _p(X), _p(Wt), _p(muf), _p(g), _p(idx), _p(start), _p(pairs), _p(post), _p(ll), F, self.D, self.C, nsel,
+                  float(min_post), _p(ws), ws.numel(), ops._stream())
+        return idx, post, ll[:F]
+
+    def stats(self, X, seg_off, order=1, idx=None, post=None, nsel=20, min_post=0.0):
+        """``slab`` (S, C, 1 + order * D) float32 as ``DiagUbm.stats``, from the full posteriors: what ``bw_stats`` and
+        ``extract_ivectors`` call, so they work on either mixture."""
+        X = self._frames(X, "FullUbm.stats")
+        if (idx is None) != (post is None):
+            raise ValueError("FullUbm.stats: idx and post come together")
+        if idx is None:
+            idx, post, _ = self.posteriors(X, nsel, min_post)
+        return self.diag().stats(X, seg_off, order, idx, post)
+
+    def full_stats(self, X, idx, post, groups=None):
+        """(C, 1 + D + Pd) float64: N, S1, S2 centred on the current means, over each Gaussian's list (``ssv_fgmm_stats``)."""
+        X = self._frames(X, "FullUbm.full_stats")
+        F = X.shape[0]
+        idx = self._idx(idx, F, "FullUbm.full_stats")
+        post = _matrix(post, "FullUbm.full_stats: post", cols=idx.shape[1])
+        if post.shape[0] != F:
+            raise ValueError("FullUbm.full_stats: post must have %d rows, got %d" % (F, post.shape[0]))
+        start, pairs = groups if groups is not None else self.group(idx)
+        nsel = idx.shape[1]
+        out = torch.empty((self.C, 1 + self.D + self.Pd), dtype=_F64, device=X.device)
+        nws = _lib.query("ssv_fgmm_stats_workspace", F, nsel, self.C, self.D)
+        ops.require_free_bytes(nws, X.device, "FullUbm.full_stats: the run sums of C=%d, D=%d need" % (self.C, self.D), "a smaller mixture")
+        ws = ops._ws(nws, X.device)
+        _lib.call("ssv_fgmm_stats", _p(X), _p(self.muf), _p(post), _p(start), _p(pairs), _p(out), F, self.D, self.C, nsel, _p(ws), ws.numel(), ops._stream())
+        return out
+
+    def update(self, stats, var_floor=1e-3, min_count=10.0, min_weight=1e-5):
+        """The M-step from ``full_stats``, in place (``ssv_fgmm_update``).  Returns ``kept`` (C,) int32: 1 where the Gaussian kept its
+        mean and covariance (starved, or a conditional variance below ``var_floor``)."""
+        stats = _matrix(stats, "FullUbm.update: stats", dtype=_F64, cols=1 + self.D + self.Pd)
+        if stats.shape[0] != self.C:
+            raise ValueError("FullUbm.update: stats must have C=%d rows, got %d" % (self.C, stats.shape[0]))
+        pl = self._planes if self._planes is not None else self._alloc_planes()
+        for t, name in ((self.w, "w"), (self.mu, "mu"), (self.cov, "cov")):
+            ops._dev(t, "FullUbm: " + name)
+        kept = torch.empty((self.C,), dtype=_I32, device=self.device)
+        _lib.call("ssv_fgmm_update", _p(stats), _p(self.w), _p(self.mu), _p(self.cov), *(_p(t) for t in pl), _p(kept), self.C, self.D,
+                  float(var_floor), float(min_count), float(min_weight), ops._stream())
+        self._planes, self._diag = pl, None
+        return kept
+
+    def em_step(self, X, idx, groups=None, var_floor=1e-3, min_count=10.0, min_weight=1e-5):
+        """One EM iteration on the selection ``idx``: posteriors (no pruning), centred statistics, the M-step.  Returns the mean
+        log-likelihood per frame over the selected under the parameters BEFORE the update (a float64 device scalar, summed as in
+        ``DiagUbm.em_step``) and ``kept``."""
+        X = self._frames(X, "FullUbm.em_step")
+        F = X.shape[0]
+        if groups is None:
+            groups = self.group(self._idx(idx, F, "FullUbm.em_step"))
+        ll = torch.zeros((-(-F // LL_ROW), LL_ROW), dtype=_F32, device=X.device)
+        idx, post, _ = self.posteriors(X, idx=idx, groups=groups, loglik_out=ll.view(-1))
+        kept = self.update(self.full_stats(X, idx, post, groups), var_floor, min_count, min_weight)
+        return DiagUbm.reduce(ll).sum() / F, kept
+
+    def fit(self, X, iters=4, nsel=20, var_floor=1e-3, min_count=10.0, min_weight=1e-5, log=print):
+        """``iters`` EM iterations on ONE selection, taken from ``self.diag()`` at the start and held (``sid/train_full_ubm.sh`` selects
+        once, with the diagonal UBM): exact EM on the truncated objective, whose history -- the mean log-likelihoods over the selected,
+        each under the parameters its iteration started from, host floats -- cannot decrease unless a Gaussian is kept or a weight floored."""
+        X = self._frames(X, "FullUbm.fit")
+        nsel = int(nsel)
+        if not 1 <= nsel <= min(self.C, MAX_NSEL):
+            raise ValueError("FullUbm.fit: nsel=%d must lie in [1, min(C=%d, %d)]" % (nsel, self.C, MAX_NSEL))
+        idx = self.diag().posteriors(X, nsel, 0.0)[0]
+        groups = self.group(idx)
+        hist = []
+        for it in range(int(iters)):
+            ll, kept = self.em_step(X, idx, groups, var_floor, min_count, min_weight)
+            hist.append(float(ll))
+            if log:
+                log("full-ubm EM %d/%d: mean log-likelihood per frame %.6f, %d Gaussians kept" % (it + 1, iters, hist[-1], int(kept.sum())))
+        return hist
+
+
+def train_full_ubm(diag_ubm, X, iters=4, nsel=20, **fit_kw):
+    """``sid/train_full_ubm.sh``: ``FullUbm.from_diag(diag_ubm)`` and ``fit(X, iters, nsel, **fit_kw)``.  Returns a namespace: ``ubm``, ``history``."""
+    ubm = FullUbm.from_diag(diag_ubm)
+    return SimpleNamespace(ubm=ubm, history=ubm.fit(X, iters, nsel, **fit_kw))
+
+
 # ------------------------------------------------------------------------------------------------------------ Baum-Welch statistics
 def plan_bw_passes(frames_per_utt, C, D, nsel, free):
     """Host planning of ``bw_stats``: the utterances go through in passes [u0, u1) whose temporaries -- the sparse posteriors of the
@@ -408,16 +623,19 @@ def product_tn(A, B, acc):
     return acc
 
 
-def plan_tv_passes(U, C, D, R, free, train):
+def plan_tv_passes(U, C, D, R, free, train, full=False):
     """Host planning of the extractor's passes over ``U`` utterances whose statistics are resident: a pass [u0, u1) holds per utterance
     Lp (P floats; training: M as well), b and w (R floats each), obj (a double) and, training, a one -- at most half of what is left of
     ``free`` after the fixed part: training, the float64 accumulators A (C, P), Cm (C D, R), Nc (C) and sum M (P); extraction, the
-    output w (U, R).  Returns (passes, need): ``need`` = the fixed part plus one utterance, the least ``free`` with which a plan exists."""
+    output w (U, R); ``full`` (a full-covariance UBM): the float64 packed inverses icov (C, D (D + 1) / 2) as well, either way.
+    Returns (passes, need): ``need`` = the fixed part plus one utterance, the least ``free`` with which a plan exists."""
     U, P = int(U), tri_size(int(R))
     if U < 1:
         raise ValueError("plan_tv_passes: need at least one utterance")
     per = P * 4 * (2 if train else 1) + R * 8 + 8 + (4 if train else 0)
     fixed = (C * P + C * D * R + C + P) * 8 if train else U * R * 4
+    if full:
+        fixed += C * tri_size(int(D)) * 8
     n = max(1, min(U, ((int(free) - fixed) // 2) // per))
     return [(u0, min(u0 + n, U)) for u0 in range(0, U, n)], fixed + per
 
@@ -446,9 +664,11 @@ def plan_extract_passes(frames_per_utt, C, D, R, nsel, free):
 
 class TotalVariability:
     """A total-variability model on one device: ``T`` (C, D, R) float64 and the UBM it stands on (``w`` (C,), ``mu``, ``var`` (C, D)
-    float64), with the float32 planes ``G`` (C D, R) and ``Pk`` (C, P) the products read, rebuilt after every update."""
+    float64), with the float32 planes ``G`` (C D, R) and ``Pk`` (C, P) the products read, rebuilt after every update.  ``cov`` (C, Pd)
+    float64, optional: the packed full covariances of a ``FullUbm``; the planes then hold Sigma^-1 in place of 1 / var
+    (``ssv_ivec_tv_planes_full``), ``var`` is their diagonal, and nothing below the planes knows the difference."""
 
-    def __init__(self, T, w, mu, var):
+    def __init__(self, T, w, mu, var, cov=None):
         for t, name in ((T, "T"), (w, "w"), (mu, "mu"), (var, "var")):
             if not isinstance(t, torch.Tensor):
                 raise ValueError("TotalVariability: %s must be a torch tensor" % name)
@@ -461,7 +681,10 @@ class TotalVariability:
             raise ValueError("TotalVariability: C=%d must lie in [1, %d], D=%d in [1, %d] and R=%d in [1, %d]" % (C, MAX_C, D, MAX_D, R, MAX_R))
         if any(t.device != T.device for t in (w, mu, var)):
             raise ValueError("TotalVariability: T, w, mu and var must live on one device")
+        if cov is not None and (not isinstance(cov, torch.Tensor) or cov.dtype != _F64 or tuple(cov.shape) != (C, tri_size(D)) or cov.device != T.device):
+            raise ValueError("TotalVariability: cov must be a float64 (C, D (D + 1) / 2) tensor on T's device")
         self.T, self.w, self.mu, self.var = (t.contiguous().clone() for t in (T, w, mu, var))
+        self.cov = None if cov is None else cov.contiguous().clone()
         self._planes = self._ubm = None
 
     C = property(lambda self: self.T.shape[0])
@@ -471,13 +694,17 @@ class TotalVariability:
     device = property(lambda self: self.T.device)
 
     def planes(self):
-        """(G, Pk) of the current ``T`` (``ssv_ivec_tv_planes``): built at first use, rebuilt by every update."""
+        """(G, Pk) of the current ``T`` (``ssv_ivec_tv_planes``; with ``cov``, ``ssv_ivec_tv_planes_full`` on the UBM's ``icov``): built at
+        first use, rebuilt by every update."""
         if self._planes is None:
             for t, name in ((self.T, "T"), (self.var, "var")):
                 ops._dev(t, "TotalVariability: " + name)
             G = torch.empty((self.C * self.D, self.R), dtype=_F32, device=self.device)
             Pk = torch.empty((self.C, self.P), dtype=_F32, device=self.device)
-            _lib.call("ssv_ivec_tv_planes", _p(self.T), _p(self.var), _p(G), _p(Pk), self.C, self.D, self.R, ops._stream())
+            if self.cov is None:
+                _lib.call("ssv_ivec_tv_planes", _p(self.T), _p(self.var), _p(G), _p(Pk), self.C, self.D, self.R, ops._stream())
+            else:
+                _lib.call("ssv_ivec_tv_planes_full", _p(self.T), _p(self.ubm().icov), _p(G), _p(Pk), self.C, self.D, self.R, ops._stream())
             self._planes = (G, Pk)
         return self._planes
 
@@ -486,33 +713,37 @@ class TotalVariability:
 
     def ubm(self):
         if self._ubm is None:
-            self._ubm = DiagUbm(self.w, self.mu, self.var)
+            self._ubm = DiagUbm(self.w, self.mu, self.var) if self.cov is None else FullUbm(self.w, self.mu, self.cov)
         return self._ubm
 
     # ------------------------------------------------------------------ state
     def state_dict(self):
-        return {"T": self.T.clone(), "w": self.w.clone(), "mu": self.mu.clone(), "var": self.var.clone()}
+        sd = {"T": self.T.clone(), "w": self.w.clone(), "mu": self.mu.clone(), "var": self.var.clone()}
+        if self.cov is not None:
+            sd["cov"] = self.cov.clone()
+        return sd
 
     def save(self, path):
-        """``.npz`` with the float64 ``T``, ``w``, ``mu``, ``var`` (the planes are derived)."""
+        """``.npz`` with the float64 ``T``, ``w``, ``mu``, ``var`` and, when set, ``cov`` (the planes are derived)."""
         np.savez(path, **{k: v.cpu().numpy() for k, v in self.state_dict().items()})
 
     @classmethod
     def load(cls, path, device="cuda"):
         """``device="cpu"`` gives a state holder only; the operations need a ROCm device."""
         with np.load(path) as z:
-            return cls(*(torch.from_numpy(np.asarray(z[k], dtype=np.float64)).to(device) for k in ("T", "w", "mu", "var")))
+            keys = ("T", "w", "mu", "var") + (("cov",) if "cov" in z.files else ())
+            return cls(*(torch.from_numpy(np.asarray(z[k], dtype=np.float64)).to(device) for k in keys))
 
     @classmethod
     def from_ubm(cls, ubm, R, seed=0):
         """The starting point of EM -- OURS: T_cdr = 0.1 sqrt(var_cd) z, z standard normal drawn on the host by
-        ``numpy.random.default_rng(seed)`` in (C, D, R) order."""
+        ``numpy.random.default_rng(seed)`` in (C, D, R) order.  ``ubm``: a ``DiagUbm``, or a ``FullUbm`` (var = diag Sigma; its ``cov`` is kept)."""
         R = int(R)
         if not 1 <= R <= MAX_R:
             raise ValueError("TotalVariability.from_ubm: R=%d must lie in [1, %d]" % (R, MAX_R))
         z = np.random.default_rng(seed).standard_normal((ubm.C, ubm.D, R))
         T = 0.1 * np.sqrt(ubm.var.cpu().numpy())[:, :, None] * z
-        return cls(torch.from_numpy(T).to(ubm.device), ubm.w, ubm.mu, ubm.var)
+        return cls(torch.from_numpy(T).to(ubm.device), ubm.w, ubm.mu, ubm.var, cov=getattr(ubm, "cov", None))
 
     # ------------------------------------------------------------------ operations
     def estep(self, N, Ft, want_M=False, w_out=None):
@@ -529,7 +760,7 @@ class TotalVariability:
         return SimpleNamespace(w=w, obj=obj, M=M, Lp=Lp, b=b)
 
     def _passes(self, U, dev, train, who):
-        passes, need = plan_tv_passes(U, self.C, self.D, self.R, ops.free_bytes(dev), train)
+        passes, need = plan_tv_passes(U, self.C, self.D, self.R, ops.free_bytes(dev), train, full=self.cov is not None)
         ops.require_free_bytes(need, dev, "%s: %d utterances at C=%d, D=%d, R=%d need" % (who, U, self.C, self.D, self.R), "a smaller rank or UBM")
         return passes
 
