@@ -1,35 +1,22 @@
 // C-ABI entries of the full-covariance UBM (include/ssv_hip.h, "I-vector groundwork: full-covariance UBM"): the argument checks, the
-// limits and the workspace layouts, all before any launch and without a device; the kernels are in fgmm.hip.
+// run counts and the workspace layouts, all before any launch and without a device; the kernels are in fgmm.hip, the limits, the two tile
+// sizes and the launchers' declarations in ivec_chain.h.
 #include "ssv_host.h"
+#include "ivec_chain.h"
 
-#pragma GCC visibility push(hidden)      // defined in fgmm.hip
-int fgmm_launch_planes(const double* w, const double* mu, const double* cov, float* Wt, float* muf, float* g, double* icov, int C, int D, hipStream_t st);
-int fgmm_launch_group(const int* idx, int* start, int* pairs, int* counts, long n, int C, hipStream_t st);
-int fgmm_launch_post(const float* X, const float* Wt, const float* muf, const float* g, const int* idx, const int* start, const int* pairs, float* post,
-                     float* loglik, float* L, long F, int D, int C, int nsel, int nrun, float min_post, hipStream_t st);
-int fgmm_launch_stats(const float* X, const float* muf, const float* post, const int* start, const int* pairs, float* slab, long F, int D, int C, int nsel,
-                      int nrun, hipStream_t st);
-int fgmm_launch_update(const double* stats, double* w, double* mu, double* cov, float* Wt, float* muf, float* g, double* icov, int* kept, int C, int D,
-                       double var_floor, double min_count, double min_weight, hipStream_t st);
-int fgmm_launch_tv_planes(const double* T, const double* icov, float* G, float* Pk, int C, int D, int R, hipStream_t st);
-int ivec_launch_reduce(const float* slab, double* out, int S, long n, hipStream_t st);      // ivector.hip
-#pragma GCC visibility pop
-
-#define FGMM_TILE 64                // = FG_TILE of fgmm.hip
-#define FGMM_SL 4096                // = FG_SL
 #define FGMM_POST_RUNS 16           // most runs a list is split into by the likelihood kernel ...
 #define FGMM_STATS_RUNS 8           // ... and by the statistics, whose slab grows with them
 
 static int fgmm_cd_ok(const char* what, int C, int D) {
   SSV_CHECK(C >= 1 && D >= 1, SSV_BAD_SHAPE, "%s: need C >= 1 and D >= 1; got C=%d D=%d", what, C, D);
-  SSV_CHECK(C <= 2048 && D <= 128, SSV_UNSUPPORTED, "%s: C=%d (at most 2048) or D=%d (at most 128) beyond the kernels", what, C, D);
+  SSV_CHECK(C <= IVEC_MAX_C && D <= IVEC_MAX_D, SSV_UNSUPPORTED, "%s: C=%d (at most %d) or D=%d (at most %d) beyond the kernels", what, C, IVEC_MAX_C, D, IVEC_MAX_D);
   return 0;
 }
 
 static int fgmm_sel_ok(const char* what, long F, int nsel, int C, int D) {
   SSV_CHECK(F >= 1 && nsel >= 1, SSV_BAD_SHAPE, "%s: need F >= 1 and nsel >= 1; got F=%ld nsel=%d", what, F, nsel);
   SSV_TRY(fgmm_cd_ok(what, C, D));
-  SSV_CHECK(nsel <= 32, SSV_UNSUPPORTED, "%s: nsel=%d beyond 32", what, nsel);
+  SSV_CHECK(nsel <= IVEC_MAX_NSEL, SSV_UNSUPPORTED, "%s: nsel=%d beyond %d", what, nsel, IVEC_MAX_NSEL);
   SSV_CHECK(F <= 0x7fffffffL / nsel, SSV_UNSUPPORTED, "%s: %ld frames x %d selected exceed the int32 slots", what, F, nsel);
   return 0;
 }
@@ -43,23 +30,23 @@ static int fgmm_runs(long F, int nsel, int C, int cap) {
 extern "C" int ssv_fgmm_pair_tile(void) { return FGMM_TILE; }
 
 extern "C" int ssv_fgmm_stats_runs(long F, int nsel, int C) {
-  if (F < 1 || nsel < 1 || nsel > 32 || C < 1 || C > 2048 || F > 0x7fffffffL / nsel) return 0;
+  if (F < 1 || nsel < 1 || nsel > IVEC_MAX_NSEL || C < 1 || C > IVEC_MAX_C || F > 0x7fffffffL / nsel) return 0;
   return fgmm_runs(F, nsel, C, FGMM_STATS_RUNS);
 }
 
 extern "C" long ssv_fgmm_group_workspace(long F, int nsel, int C) {
-  if (F < 1 || nsel < 1 || nsel > 32 || C < 1 || C > 2048 || F > 0x7fffffffL / nsel) return 0;
+  if (F < 1 || nsel < 1 || nsel > IVEC_MAX_NSEL || C < 1 || C > IVEC_MAX_C || F > 0x7fffffffL / nsel) return 0;
   return (long)align256((size_t)((F * nsel + FGMM_SL - 1) / FGMM_SL) * C * sizeof(int));
 }
 
 extern "C" long ssv_fgmm_post_workspace(long F, int nsel) {
-  if (F < 1 || nsel < 1 || nsel > 32 || F > 0x7fffffffL / nsel) return 0;
+  if (F < 1 || nsel < 1 || nsel > IVEC_MAX_NSEL || F > 0x7fffffffL / nsel) return 0;
   return (long)align256((size_t)F * nsel * sizeof(float));
 }
 
 extern "C" long ssv_fgmm_stats_workspace(long F, int nsel, int C, int D) {
   const int runs = ssv_fgmm_stats_runs(F, nsel, C);
-  if (!runs || D < 1 || D > 128) return 0;
+  if (!runs || D < 1 || D > IVEC_MAX_D) return 0;
   return (long)align256((size_t)runs * C * (1 + D + (size_t)D * (D + 1) / 2) * sizeof(float));
 }
 
@@ -116,6 +103,6 @@ extern "C" int ssv_ivec_tv_planes_full(const double* T, const double* icov, floa
   SSV_CHECK(T && icov && G && Pk, SSV_BAD_SHAPE, "ivec_tv_planes_full: null pointer (T, icov, G and Pk are required)");
   SSV_CHECK(R >= 1, SSV_BAD_SHAPE, "ivec_tv_planes_full: need R >= 1; got R=%d", R);
   SSV_TRY(fgmm_cd_ok("ivec_tv_planes_full", C, D));
-  SSV_CHECK(R <= 192, SSV_UNSUPPORTED, "ivec_tv_planes_full: R=%d beyond 192", R);
+  SSV_CHECK(R <= IVEC_MAX_R, SSV_UNSUPPORTED, "ivec_tv_planes_full: R=%d beyond %d", R, IVEC_MAX_R);
   return fgmm_launch_tv_planes(T, icov, G, Pk, C, D, R, (hipStream_t)stream);
 }

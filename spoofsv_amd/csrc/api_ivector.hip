@@ -1,19 +1,8 @@
 // C-ABI entries of the i-vector front half (include/ssv_hip.h, "I-vector groundwork"): the argument checks, which come before any launch
-// and need no device; the kernels and their tile limits are in ivector.hip.
+// and need no device; the kernels are in ivector.hip, the limits and the launchers' declarations in ivec_chain.h.
 #include "ssv_host.h"
-
-#pragma GCC visibility push(hidden)      // defined in ivector.hip
-int ivec_launch_features(const float* mel, const long* utt_off, const float* dct, float* out, float* v, long G, int M, int U, int Cc, int order, int w, int W,
-                         hipStream_t st);
-int ivec_gselect_tile(int D, int C, size_t* lds_bytes);
-int ivec_launch_gselect(const float* X, const float* A, const float* B, const float* g, int* idx, float* post, float* loglik, long F, int D, int C, int nsel,
-                        float min_post, hipStream_t st);
-int ivec_launch_stats(const float* X, const int* idx, const float* post, const long* seg_off, float* slab, long F, int D, int C, int nsel, int S, int order,
-                      hipStream_t st);
-int ivec_launch_reduce(const float* slab, double* out, int S, long n, hipStream_t st);
-int ivec_launch_update(const double* stats, const double* w_in, double* w_out, double* mu, double* var, float* A, float* B, float* g, int C, int D,
-                       double var_floor, double min_count, double min_weight, hipStream_t st);
-#pragma GCC visibility pop
+#include "ivec_chain.h"
+#include "exact_product.h"        // XP_RUN, XP_TILE
 
 extern "C" long ssv_ivec_features_workspace(long G, int Cc, int delta_order) {
   if (G < 1 || Cc < 1 || delta_order < 0 || delta_order > 2) return 0;
@@ -56,11 +45,7 @@ extern "C" int ssv_gmm_diag_stats(const float* X, const int* idx, const float* p
   SSV_CHECK(F >= 1 && D >= 1 && C >= 1 && nsel >= 1 && nsel <= C && S >= 1, SSV_BAD_SHAPE,
             "gmm_diag_stats: need F >= 1, D >= 1, 1 <= nsel <= C and S >= 1; got F=%ld D=%d C=%d nsel=%d S=%d", F, D, C, nsel, S);
   SSV_CHECK(order == 1 || order == 2, SSV_BAD_SHAPE, "gmm_diag_stats: order=%d must be 1 or 2", order);
-  if (seg_off_host) {
-    SSV_CHECK(seg_off_host[0] >= 0 && seg_off_host[S] <= F, SSV_BAD_SHAPE, "gmm_diag_stats: segments [%ld, %ld) leave the %ld frames", seg_off_host[0], seg_off_host[S], F);
-    for (int s = 0; s < S; ++s)
-      SSV_CHECK(seg_off_host[s] <= seg_off_host[s + 1], SSV_BAD_SHAPE, "gmm_diag_stats: seg_off descends at segment %d (%ld > %ld)", s, seg_off_host[s], seg_off_host[s + 1]);
-  }
+  SSV_TRY(host_offsets_ok("gmm_diag_stats", "seg_off", "segment", "frames", seg_off_host, S, F));
   return ivec_launch_stats(X, idx, post, seg_off, slab, F, D, C, nsel, S, order, (hipStream_t)stream);
 }
 
@@ -73,7 +58,8 @@ extern "C" int ssv_gmm_stats_reduce(const float* slab, double* out, int S, long 
 
 static int gmm_cd_ok(const char* what, int C, int D) {
   SSV_CHECK(C >= 1 && D >= 1, SSV_BAD_SHAPE, "%s: need C >= 1 and D >= 1; got C=%d D=%d", what, C, D);
-  SSV_CHECK(C <= 2048 && D <= 128, SSV_UNSUPPORTED, "%s: C=%d (at most 2048) or D=%d (at most 128) beyond what the other entries take", what, C, D);
+  SSV_CHECK(C <= IVEC_MAX_C && D <= IVEC_MAX_D, SSV_UNSUPPORTED, "%s: C=%d (at most %d) or D=%d (at most %d) beyond what the other entries take", what, C, IVEC_MAX_C, D,
+            IVEC_MAX_D);
   return 0;
 }
 
@@ -92,17 +78,7 @@ extern "C" int ssv_gmm_diag_planes(const double* w, const double* mu, const doub
   return ivec_launch_update(nullptr, w, nullptr, (double*)mu, (double*)var, A, B, g, C, D, 1.0, 0.0, 0.5, (hipStream_t)stream);
 }
 
-// ---- the i-vector extractor (include/ssv_hip.h, "I-vector extractor"): kernels and tile limits in ivector_tv.hip -------------------------
-#pragma GCC visibility push(hidden)      // defined in ivector_tv.hip
-int tv_launch_planes(const double* T, const double* var, float* G, float* Pk, int C, int D, int R, hipStream_t st);
-int tv_launch_centre(const float* N, const float* F, const double* mu, float* Ft, long U, int C, int D, hipStream_t st);
-int tv_launch_product(const float* A, const float* B, float* out, long m, long n, long K, hipStream_t st);
-int tv_launch_product_tn(const float* A, const float* B, double* acc, long U, long m, long n, hipStream_t st);
-int tv_launch_estep(const float* Lp, const float* b, float* w, float* M, double* obj, long U, int R, hipStream_t st);
-int tv_launch_update(const double* A, const double* Cm, const double* Nc, const double* J, double* T, int C, int D, int R, double min_count, hipStream_t st);
-int tv_launch_cosine(const float* enroll, const long* spk_off, const float* evalv, float* scores, long n_enroll, int S, long E, int R, hipStream_t st);
-#pragma GCC visibility pop
-
+// ---- the i-vector extractor (include/ssv_hip.h, "I-vector extractor"): kernels in ivector_tv.hip ------------------------------------------
 extern "C" int ssv_ivec_tv_planes(const double* T, const double* var, float* G, float* Pk, int C, int D, int R, ssv_stream_t stream) {
   SSV_CHECK(T && var && G && Pk, SSV_BAD_SHAPE, "ivec_tv_planes: null pointer (T, var, G and Pk are required)");
   SSV_CHECK(C >= 1 && D >= 1 && R >= 1, SSV_BAD_SHAPE, "ivec_tv_planes: need C >= 1, D >= 1 and R >= 1; got C=%d D=%d R=%d", C, D, R);
@@ -115,8 +91,8 @@ extern "C" int ssv_ivec_centre_stats(const float* N, const float* F, const doubl
   return tv_launch_centre(N, F, mu, Ft, U, C, D, (hipStream_t)stream);
 }
 
-extern "C" int ssv_ivec_product_run(void) { return 256; }
-extern "C" int ssv_ivec_product_tile(void) { return 64; }
+extern "C" int ssv_ivec_product_run(void) { return XP_RUN; }
+extern "C" int ssv_ivec_product_tile(void) { return XP_TILE; }
 
 extern "C" int ssv_ivec_product(const float* A, const float* B, float* out, long m, long n, long K, ssv_stream_t stream) {
   SSV_CHECK(A && B && out, SSV_BAD_SHAPE, "ivec_product: null pointer (A, B and out are required)");
@@ -149,12 +125,6 @@ extern "C" int ssv_ivec_cosine_trials(const float* enroll, const long* spk_off, 
   SSV_CHECK(enroll && spk_off && evalv && scores, SSV_BAD_SHAPE, "ivec_cosine_trials: null pointer (enroll, spk_off, evalv and scores are required)");
   SSV_CHECK(n_enroll >= 1 && S >= 1 && E >= 1 && R >= 1, SSV_BAD_SHAPE, "ivec_cosine_trials: need n_enroll >= 1, S >= 1, E >= 1 and R >= 1; got n_enroll=%ld S=%d E=%ld R=%d",
             n_enroll, S, E, R);
-  if (spk_off_host) {
-    SSV_CHECK(spk_off_host[0] >= 0 && spk_off_host[S] <= n_enroll, SSV_BAD_SHAPE, "ivec_cosine_trials: speakers [%ld, %ld) leave the %ld enrolment vectors",
-              spk_off_host[0], spk_off_host[S], n_enroll);
-    for (int s = 0; s < S; ++s)
-      SSV_CHECK(spk_off_host[s] <= spk_off_host[s + 1], SSV_BAD_SHAPE, "ivec_cosine_trials: spk_off descends at speaker %d (%ld > %ld)", s, spk_off_host[s],
-                spk_off_host[s + 1]);
-  }
+  SSV_TRY(host_offsets_ok("ivec_cosine_trials", "spk_off", "speaker", "enrolment vectors", spk_off_host, S, n_enroll));
   return tv_launch_cosine(enroll, spk_off, evalv, scores, n_enroll, S, E, R, (hipStream_t)stream);
 }

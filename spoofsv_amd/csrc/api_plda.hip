@@ -1,30 +1,12 @@
 // C-ABI entries of the i-vector back end (include/ssv_hip.h, "I-vector back end: PLDA"): the argument checks, which come before any launch
-// and need no device; the kernels and their limits are in plda.hip, the product of the transform in ivector_tv.hip.
+// and need no device; the kernels are in plda.hip, the product of the transform in ivector_tv.hip, the rank limit and the launchers'
+// declarations in ivec_chain.h.
 #include "ssv_host.h"
-
-#pragma GCC visibility push(hidden)      // defined in plda.hip
-int plda_launch_class_stats(const float* X, const long* spk_off, float* Xd, double* means, double* mu, float* model, long n, int S, int R, int length_norm,
-                            hipStream_t st);
-int plda_launch_mixed_inverse(const double* a, const double* b, long b_stride, const double* coef, double* out, double* logdet, int J, int R, hipStream_t st);
-int plda_launch_em_classes(const double* means, const double* mu, const int* cnt, const int* cls, const double* Mx, const double* Winv, double* w, double* r,
-                           double* quad, int S, int R, int J, hipStream_t st);
-int plda_launch_wsyrk(const double* V, const double* c, double* acc, long S, int R, hipStream_t st);
-int plda_launch_em_update(const double* Mx, const double* ldMx, const double* nspk, const double* nrow, const double* WW, const double* RR, const double* Sigma,
-                          const double* Winv, const double* ldW, const double* ldB, const int* cnt, const int* cls, const double* quad, double* W, double* B,
-                          double* obj, int J, int S, int R, double Sn, double N, hipStream_t st);
-int plda_launch_centre(const float* X, const double* mu, float* Xc, long n, int R, int length_norm, hipStream_t st);
-int plda_launch_scale(float* U, const double* psi, const int* nex, int nex_all, long n, int R, hipStream_t st);
-int plda_launch_speaker_planes(const float* y, const int* nspk, const double* psi, float* H, double* k, int S, int R, hipStream_t st);
-int plda_launch_score(const float* T, const float* H, const double* k, float* scores, long E, long S, int R, hipStream_t st);
-// defined in ivector_tv.hip
-int tv_launch_product(const float* A, const float* B, float* out, long m, long n, long K, hipStream_t st);
-#pragma GCC visibility pop
-
-#define PLDA_MAX_R 192
+#include "ivec_chain.h"
 
 static int plda_rank(const char* what, int R) {
   SSV_CHECK(R >= 1, SSV_BAD_SHAPE, "%s: need R >= 1; got R=%d", what, R);
-  SSV_CHECK(R <= PLDA_MAX_R, SSV_UNSUPPORTED, "%s: R=%d (at most %d) beyond the kernels", what, R, PLDA_MAX_R);
+  SSV_CHECK(R <= IVEC_MAX_R, SSV_UNSUPPORTED, "%s: R=%d (at most %d) beyond the kernels", what, R, IVEC_MAX_R);
   return 0;
 }
 
@@ -35,12 +17,7 @@ extern "C" int ssv_plda_class_stats(const float* X, const long* spk_off, const l
   SSV_CHECK(!mu || means, SSV_BAD_SHAPE, "plda_class_stats: mu is the mean of the means: means is required with it");
   SSV_CHECK(n >= 1 && S >= 1, SSV_BAD_SHAPE, "plda_class_stats: need n >= 1 and S >= 1; got n=%ld S=%d", n, S);
   SSV_TRY(plda_rank("plda_class_stats", R));
-  if (spk_off_host) {
-    SSV_CHECK(spk_off_host[0] >= 0 && spk_off_host[S] <= n, SSV_BAD_SHAPE, "plda_class_stats: speakers [%ld, %ld) leave the %ld rows", spk_off_host[0], spk_off_host[S], n);
-    for (int s = 0; s < S; ++s)
-      SSV_CHECK(spk_off_host[s] <= spk_off_host[s + 1], SSV_BAD_SHAPE, "plda_class_stats: spk_off descends at speaker %d (%ld > %ld)", s, spk_off_host[s],
-                spk_off_host[s + 1]);
-  }
+  SSV_TRY(host_offsets_ok("plda_class_stats", "spk_off", "speaker", "rows", spk_off_host, S, n));
   return plda_launch_class_stats(X, spk_off, Xd, means, mu, model, n, S, R, length_norm != 0, (hipStream_t)stream);
 }
 

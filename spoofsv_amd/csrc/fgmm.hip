@@ -2,48 +2,18 @@
 // mixture (Cholesky, triangular inverse and W^T W of the packed float64 triangle in LDS, tv_triangle.h), the Gaussian-major selection
 // lists (a stable counting sort of the slots f * nsel + j by their Gaussian), the log-likelihoods and posteriors over the selected pairs,
 // the centred second-order statistics over each Gaussian's list, the M-step and the extractor's planes G = Sigma^-1 T, Pk = T^T G.
-// The two hot kernels walk a Gaussian's list in tiles of FG_TILE pairs: the pairs' frame rows are gathered into LDS and centred on the
+// The two hot kernels walk a Gaussian's list in tiles of FGMM_TILE pairs: the pairs' frame rows are gathered into LDS and centred on the
 // Gaussian's float32 mean (one subtraction, before any product), and the products run on v_mfma_f32_16x16x4_f32 whatever
 // ssv_set_precision says -- K is D (likelihoods) or 64 pairs (statistics), so the fp32 rate is not what limits them (ivector.hip).  What
 // a workgroup stages once -- Wt_c, 14 KB at D = 60 -- serves all pairs of its run: that sharing is the point of the Gaussian-major order.
 // No float atomics anywhere (the counting sort adds INTEGERS in LDS, and no position depends on them arriving in any order); every sum
 // runs in an order fixed by the shapes and the selection lists alone: the same inputs give the same bits.
 // This file holds the kernels and their launchers; api_fgmm.hip holds the C-ABI entries and the argument checks.
-#include <atomic>
-#include "ssv_common.h"
-#include "tv_triangle.h"
+#include "tv_triangle.h"          // the packed triangle, tv_wg_sum, tv_lds_limit_set; the limits, FGMM_TILE, FGMM_SL and the launchers (ivec_chain.h)
 
-#define FG_MAX_D 128
-#define FG_MAX_C 2048
-#define FG_TILE 64                  // pairs one workgroup of the product kernels owns per step (ssv_fgmm_pair_tile)
-#define FG_SL 4096                  // slots per workgroup of the counting sort
 #define FG_SB 32                    // extractor planes: columns of T one workgroup owns
 
-#pragma GCC visibility push(hidden)      // the launchers: called by api_fgmm.hip (which repeats these lines), not exported
-int fgmm_launch_planes(const double* w, const double* mu, const double* cov, float* Wt, float* muf, float* g, double* icov, int C, int D, hipStream_t st);
-int fgmm_launch_group(const int* idx, int* start, int* pairs, int* counts, long n, int C, hipStream_t st);
-int fgmm_launch_post(const float* X, const float* Wt, const float* muf, const float* g, const int* idx, const int* start, const int* pairs, float* post,
-                     float* loglik, float* L, long F, int D, int C, int nsel, int nrun, float min_post, hipStream_t st);
-int fgmm_launch_stats(const float* X, const float* muf, const float* post, const int* start, const int* pairs, float* slab, long F, int D, int C, int nsel,
-                      int nrun, hipStream_t st);
-int fgmm_launch_update(const double* stats, double* w, double* mu, double* cov, float* Wt, float* muf, float* g, double* icov, int* kept, int C, int D,
-                       double var_floor, double min_count, double min_weight, hipStream_t st);
-int fgmm_launch_tv_planes(const double* T, const double* icov, float* G, float* Pk, int C, int D, int R, hipStream_t st);
-#pragma GCC visibility pop
-
 // ---- planes and M-step -----------------------------------------------------------------------------------------------------------------
-// sum of a per-thread double over the 256 threads, every thread gets it; the tree's shape is fixed
-__device__ __forceinline__ double fg_wg_sum(double v, double* sm) {
-  __syncthreads();
-  sm[threadIdx.x] = v;
-  __syncthreads();
-  for (int s = 128; s > 0; s >>= 1) {
-    if ((int)threadIdx.x < s) sm[threadIdx.x] += sm[threadIdx.x + s];
-    __syncthreads();
-  }
-  return sm[0];
-}
-
 // tri = packed Sigma -> its Cholesky factor in place; logdet = log|Sigma| from the pivots.  False at a pivot that is not positive or, with
 // floor > 0, when some L_ii^2 < floor (the conditional variance of dimension i given those before it).  Every thread reads the same
 // values from LDS, so the whole workgroup takes the same branch.
@@ -151,13 +121,13 @@ __global__ __launch_bounds__(256) void fgmm_weights_kernel(const double* __restr
   const int tid = threadIdx.x;
   double p = 0.0;
   for (int i = tid; i < C; i += 256) p += stats[(long)i * NV];
-  const double ntot = fg_wg_sum(p, sm);
+  const double ntot = tv_wg_sum(p, sm);
   p = 0.0;
   for (int i = tid; i < C; i += 256) {
     const double wi = stats[(long)i * NV] / ntot;
     p += kept[i] ? fmax(wi, min_weight) : wi;
   }
-  const double wtot = fg_wg_sum(p, sm);
+  const double wtot = tv_wg_sum(p, sm);
   for (int i = tid; i < C; i += 256) {
     const double wi = stats[(long)i * NV] / ntot, wc = (kept[i] ? fmax(wi, min_weight) : wi) / wtot, gp = w[i];
     w[i] = wc;
@@ -166,16 +136,16 @@ __global__ __launch_bounds__(256) void fgmm_weights_kernel(const double* __restr
 }
 
 // ---- the Gaussian-major selection lists ----------------------------------------------------------------------------------------------
-// A stable counting sort of the n = F nsel slots by idx[slot], in three steps over blocks of FG_SL slots:
+// A stable counting sort of the n = F nsel slots by idx[slot], in three steps over blocks of FGMM_SL slots:
 //   count:   counts[b][c] = slots of block b whose idx is c (integer adds in LDS);
 //   prefix:  per c, counts[b][c] <- the slots of c in the blocks before b, and the list's length; one wave then scans the lengths to start;
 //   scatter: ONE wave per block walks its slots in ascending order, 64 at a time; a lane's position is start[c] + counts[b][c] + the slots
 //            of c the block has placed so far + the lanes below it that hold the same c (found by ballots over the 11 bits of c).
 // Nothing in a position depends on the order in which workgroups or lanes ran.
 __global__ __launch_bounds__(256) void fgmm_count_kernel(const int* __restrict__ idx, int* __restrict__ counts, long n, int C) {
-  __shared__ int cnt[FG_MAX_C];
+  __shared__ int cnt[IVEC_MAX_C];
   const int tid = threadIdx.x;
-  const long s0 = (long)blockIdx.x * FG_SL, s1 = min(s0 + FG_SL, n);
+  const long s0 = (long)blockIdx.x * FGMM_SL, s1 = min(s0 + FGMM_SL, n);
   for (int c = tid; c < C; c += 256) cnt[c] = 0;
   __syncthreads();
   for (long s = s0 + tid; s < s1; s += 256) {
@@ -217,9 +187,9 @@ __global__ __launch_bounds__(64) void fgmm_scan_kernel(int* __restrict__ start, 
 
 __global__ __launch_bounds__(64) void fgmm_scatter_kernel(const int* __restrict__ idx, const int* __restrict__ counts, const int* __restrict__ start,
                                                           int* __restrict__ pairs, long n, int C) {
-  __shared__ int cnt[FG_MAX_C];
+  __shared__ int cnt[IVEC_MAX_C];
   const int lane = threadIdx.x;
-  const long s0 = (long)blockIdx.x * FG_SL, s1 = min(s0 + FG_SL, n);
+  const long s0 = (long)blockIdx.x * FGMM_SL, s1 = min(s0 + FGMM_SL, n);
   for (int c = lane; c < C; c += 64) cnt[c] = start[c] + counts[(long)blockIdx.x * C + c];
   __syncthreads();
   for (long sb = s0; sb < s1; sb += 64) {
@@ -249,7 +219,7 @@ __global__ __launch_bounds__(64) void fgmm_scatter_kernel(const int* __restrict_
 // ---- log-likelihoods over the selected pairs ---------------------------------------------------------------------------------------------
 // the run [t0, t1) of tiles that workgroup r of nrun owns in a list of len pairs: it follows from len and nrun alone
 __device__ __forceinline__ void fg_run(int len, int r, int nrun, int& t0, int& t1) {
-  const int nt = (len + FG_TILE - 1) / FG_TILE, per = (nt + nrun - 1) / nrun;
+  const int nt = (len + FGMM_TILE - 1) / FGMM_TILE, per = (nt + nrun - 1) / nrun;
   t0 = min(r * per, nt);
   t1 = min(t0 + per, nt);
 }
@@ -259,14 +229,14 @@ __device__ __forceinline__ void fg_run(int len, int r, int nrun, int& t0, int& t
 __device__ __forceinline__ void fg_gather(const float* __restrict__ X, const int* __restrict__ pairs, const float* mus, int* sl, int* fr, float* Xs, long p0,
                                           long pend, long n, long F, int D, int nsel, int DP, int XS) {
   const int tid = threadIdx.x;
-  if (tid < FG_TILE) {
+  if (tid < FGMM_TILE) {
     int slot = p0 + tid < pend ? pairs[p0 + tid] : -1;
     if (slot < 0 || slot >= n) slot = -1;
     sl[tid] = slot;
     fr[tid] = slot < 0 ? -1 : slot / nsel;
   }
   __syncthreads();
-  for (int e = tid; e < FG_TILE * DP; e += 256) {
+  for (int e = tid; e < FGMM_TILE * DP; e += 256) {
     const int r = e / DP, d = e - r * DP, f = fr[r];
     Xs[r * XS + d] = (f >= 0 && f < F && d < D) ? X[(long)f * D + d] - mus[d] : 0.f;
   }
@@ -284,10 +254,10 @@ __global__ __launch_bounds__(256) void fgmm_like_kernel(const float* __restrict_
   extern __shared__ __attribute__((aligned(16))) float lds[];      // all of the kernel's LDS is dynamic: the raised limit counts static LDS on top
   const int XS = DP + 4;
   float* Ws = lds;                        // [DP][XS]
-  float* Xs = lds + DP * XS;              // [FG_TILE][XS]
-  int* sl = reinterpret_cast<int*>(Xs + FG_TILE * XS);      // [FG_TILE]
-  int* fr = sl + FG_TILE;                 // [FG_TILE]
-  float* mus = reinterpret_cast<float*>(fr + FG_TILE);      // [FG_MAX_D]
+  float* Xs = lds + DP * XS;              // [FGMM_TILE][XS]
+  int* sl = reinterpret_cast<int*>(Xs + FGMM_TILE * XS);      // [FGMM_TILE]
+  int* fr = sl + FGMM_TILE;               // [FGMM_TILE]
+  float* mus = reinterpret_cast<float*>(fr + FGMM_TILE);      // [IVEC_MAX_D]
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, kq = lane >> 4, cq = lane & 15;
   const int c = blockIdx.x / nrun, r = blockIdx.x - c * nrun;
   const long n = F * nsel;
@@ -305,7 +275,7 @@ __global__ __launch_bounds__(256) void fgmm_like_kernel(const float* __restrict_
   const int nib = DP >> 4;
   for (int t = t0; t < t1; ++t) {
     __syncthreads();                      // the tile before has been read (first tile: mus is written)
-    fg_gather(X, pairs, mus, sl, fr, Xs, a + (long)t * FG_TILE, b, n, F, D, nsel, DP, XS);
+    fg_gather(X, pairs, mus, sl, fr, Xs, a + (long)t * FGMM_TILE, b, n, F, D, nsel, DP, XS);
     float sq[4] = {0.f, 0.f, 0.f, 0.f};
     for (int ib = 0; ib < nib; ++ib) {
       f32x4 acc = (f32x4){0.f, 0.f, 0.f, 0.f};
@@ -390,10 +360,10 @@ __global__ __launch_bounds__(256) void fgmm_stats_kernel(const float* __restrict
                                                          const int* __restrict__ start, const int* __restrict__ pairs, float* __restrict__ slab, long F, int D,
                                                          int C, int nsel, int nrun, int DP) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
-  __shared__ int sl[FG_TILE], fr[FG_TILE];
-  __shared__ float mus[FG_MAX_D], gam[FG_TILE];
+  __shared__ int sl[FGMM_TILE], fr[FGMM_TILE];
+  __shared__ float mus[IVEC_MAX_D], gam[FGMM_TILE];
   const int XS = DP + 4;
-  float* Xs = lds;                        // [FG_TILE][XS]
+  float* Xs = lds;                        // [FGMM_TILE][XS]
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, kq = lane >> 4, cq = lane & 15;
   const int c = blockIdx.x / nrun, r = blockIdx.x - c * nrun;
   const long n = F * nsel;
@@ -419,8 +389,8 @@ __global__ __launch_bounds__(256) void fgmm_stats_kernel(const float* __restrict
   double s1 = 0.0;
   for (int t = t0; t < t1; ++t) {
     __syncthreads();
-    fg_gather(X, pairs, mus, sl, fr, Xs, a + (long)t * FG_TILE, b, n, F, D, nsel, DP, XS);
-    if (tid < FG_TILE) gam[tid] = sl[tid] >= 0 ? post[sl[tid]] : 0.f;
+    fg_gather(X, pairs, mus, sl, fr, Xs, a + (long)t * FGMM_TILE, b, n, F, D, nsel, DP, XS);
+    if (tid < FGMM_TILE) gam[tid] = sl[tid] >= 0 ? post[sl[tid]] : 0.f;
     __syncthreads();
 #pragma unroll
     for (int i = 0; i < NBW; ++i) {
@@ -429,7 +399,7 @@ __global__ __launch_bounds__(256) void fgmm_stats_kernel(const float* __restrict
       const float* ar = Xs + rbk[i] * 16 + cq;
       const float* br = Xs + cbk[i] * 16 + cq;
 #pragma unroll 4
-      for (int ks = 0; ks < FG_TILE / 4; ++ks) {
+      for (int ks = 0; ks < FGMM_TILE / 4; ++ks) {
         const int k = 4 * ks + kq;
         acc = __builtin_amdgcn_mfma_f32_16x16x4f32(gam[k] * ar[k * XS], br[k * XS], acc, 0, 0, 0);
       }
@@ -438,11 +408,11 @@ __global__ __launch_bounds__(256) void fgmm_stats_kernel(const float* __restrict
     }
     if (tid < D) {
       float s = 0.f;
-      for (int p = 0; p < FG_TILE; ++p) s = fmaf(gam[p], Xs[p * XS + tid], s);
+      for (int p = 0; p < FGMM_TILE; ++p) s = fmaf(gam[p], Xs[p * XS + tid], s);
       s1 += (double)s;
     } else if (tid == 255) {
       float s = 0.f;
-      for (int p = 0; p < FG_TILE; ++p) s += gam[p];
+      for (int p = 0; p < FGMM_TILE; ++p) s += gam[p];
       s1 += (double)s;
     }
   }
@@ -468,7 +438,7 @@ __global__ __launch_bounds__(256) void fgmm_stats_kernel(const float* __restrict
 // rounded once; then Pk_c (r, s) = sum_d T_c[d][r] G_c[d][s] for every r >= s, in double, rounded once: the layout of ssv_ivec_tv_planes.
 __global__ __launch_bounds__(256) void fgmm_tv_planes_kernel(const double* __restrict__ T, const double* __restrict__ icov, float* __restrict__ G,
                                                              float* __restrict__ Pk, int D, int R) {
-  __shared__ double Gb[FG_MAX_D * FG_SB];
+  __shared__ double Gb[IVEC_MAX_D * FG_SB];
   const int c = blockIdx.x, s0 = blockIdx.y * FG_SB, ns = min(FG_SB, R - s0), tid = threadIdx.x;
   const long Pd = (long)D * (D + 1) / 2, P = (long)R * (R + 1) / 2;
   const double* Tc = T + (long)c * D * R;
@@ -519,7 +489,7 @@ int fgmm_launch_update(const double* stats, double* w, double* mu, double* cov, 
 }
 
 int fgmm_launch_group(const int* idx, int* start, int* pairs, int* counts, long n, int C, hipStream_t st) {
-  const int nb = ssv_cdiv(n, FG_SL);
+  const int nb = ssv_cdiv(n, FGMM_SL);
   hipLaunchKernelGGL(fgmm_count_kernel, dim3(nb), dim3(256), 0, st, idx, counts, n, C);
   SSV_TRY(ssv_check_launch("fgmm_count"));
   hipLaunchKernelGGL(fgmm_prefix_kernel, dim3(ssv_cdiv(C, 64)), dim3(64), 0, st, counts, start, nb, C);
@@ -534,7 +504,7 @@ int fgmm_launch_post(const float* X, const float* Wt, const float* muf, const fl
                      float* loglik, float* L, long F, int D, int C, int nsel, int nrun, float min_post, hipStream_t st) {
   SSV_TRY(fg_lds_limit());
   const int DP = (D + 15) & ~15;
-  const size_t lds = ((size_t)(DP + FG_TILE) * (DP + 4) + 2 * FG_TILE + FG_MAX_D) * sizeof(float);
+  const size_t lds = ((size_t)(DP + FGMM_TILE) * (DP + 4) + 2 * FGMM_TILE + IVEC_MAX_D) * sizeof(float);
   hipLaunchKernelGGL(fgmm_like_kernel, dim3(C * nrun), dim3(256), lds, st, X, Wt, muf, g, start, pairs, L, F, D, nsel, nrun, DP);
   SSV_TRY(ssv_check_launch("fgmm_like"));
   hipLaunchKernelGGL(fgmm_finish_kernel, dim3(ssv_cdiv(F, 256)), dim3(256), 0, st, (const float*)L, idx, post, loglik, F, C, nsel, min_post);
@@ -544,7 +514,7 @@ int fgmm_launch_post(const float* X, const float* Wt, const float* muf, const fl
 int fgmm_launch_stats(const float* X, const float* muf, const float* post, const int* start, const int* pairs, float* slab, long F, int D, int C, int nsel,
                       int nrun, hipStream_t st) {
   const int DP = (D + 15) & ~15, nb = DP >> 4, nblk = nb * (nb + 1) / 2, nbw = (nblk + 3) / 4;
-  const size_t lds = (size_t)FG_TILE * (DP + 4) * sizeof(float);
+  const size_t lds = (size_t)FGMM_TILE * (DP + 4) * sizeof(float);
   const dim3 grid(C * nrun);
 #define FG_STATS(NBW_) hipLaunchKernelGGL(fgmm_stats_kernel<NBW_>, grid, dim3(256), lds, st, X, muf, post, start, pairs, slab, F, D, C, nsel, nrun, DP)
   if (nbw <= 1) FG_STATS(1);

@@ -8,36 +8,18 @@
 // No float atomics anywhere; every sum runs in an order fixed by the shapes alone: the same inputs give the same bits.
 // This file holds the kernels and their launchers, which know the tiles and refuse a shape beyond them (-2) before anything is launched;
 // api_ivector.hip holds the C-ABI entries and the argument checks (-1).
-#include <atomic>
 #include <string.h>
-#include "ssv_common.h"
+#include "tv_triangle.h"          // tv_wg_sum, TV_LDS_MAX, tv_lds_limit_set; the limits and launchers (ivec_chain.h)
 
 #define IV_FT 64                    // features: frames per workgroup of the delta pass
 #define IV_MAX_W 8                  // largest delta window (the halo is 2 w frames on each side)
 #define IV_MAX_CC 128               // most static coefficients (LDS: (IV_FT + 4 IV_MAX_W) x IV_MAX_CC floats = 48 KiB)
 #define IV_CMN_RUN 64               // mean subtraction: consecutive frames one thread slides over
-#define IV_LDS_MAX (160 * 1024)     // LDS of a CU: one workgroup of the selection kernel may take all of it
-#define IV_MAX_D 128
-#define IV_MAX_C 2048
-#define IV_MAX_NSEL 32
 #define ST_TG 64                    // statistics: Gaussians per workgroup (16 per wave)
 #define ST_TF 64                    // frames per step of the walk over a segment
 #define ST_GS (ST_TF + 4)           // row stride of the Gaussian x frame tile (16-byte rows, b128 reads 4 banks apart per row)
 #define ST_MAXB 17                  // value blocks of 16: 1 + 2 * 128 = 257 columns at most (the kernel is instantiated for 4, 12 and 17)
 struct IvecDelta { float c1[2 * IV_MAX_W + 1]; float c2[4 * IV_MAX_W + 1]; };
-
-#pragma GCC visibility push(hidden)      // the launchers: called by api_ivector.hip (which repeats these lines), not exported
-int ivec_launch_features(const float* mel, const long* utt_off, const float* dct, float* out, float* v, long G, int M, int U, int Cc, int order, int w, int W,
-                         hipStream_t st);
-int ivec_gselect_tile(int D, int C, size_t* lds_bytes);      // frames per workgroup, 0 = beyond the tiles
-int ivec_launch_gselect(const float* X, const float* A, const float* B, const float* g, int* idx, float* post, float* loglik, long F, int D, int C, int nsel,
-                        float min_post, hipStream_t st);
-int ivec_launch_stats(const float* X, const int* idx, const float* post, const long* seg_off, float* slab, long F, int D, int C, int nsel, int S, int order,
-                      hipStream_t st);
-int ivec_launch_reduce(const float* slab, double* out, int S, long n, hipStream_t st);
-int ivec_launch_update(const double* stats, const double* w_in, double* w_out, double* mu, double* var, float* A, float* B, float* g, int C, int D,
-                       double var_floor, double min_count, double min_weight, hipStream_t st);
-#pragma GCC visibility pop
 
 // utterance / segment of a compact frame index: the LAST u in [0, U) with off[u] <= g, provided g < off[u + 1] (empty utterances are
 // skipped: their two offsets are equal).  Returns false when g lies in no utterance.  The bounds come back clamped to [0, G]; the search
@@ -407,18 +389,6 @@ __global__ __launch_bounds__(256) void gmm_reduce_kernel(const float* __restrict
 }
 
 // ---- M-step ----------------------------------------------------------------------------------------------------------------------------
-// sum of a per-thread double over the workgroup, every thread gets it; the tree's shape is fixed (256 threads)
-__device__ __forceinline__ double iv_wg_sum(double v, double* sm) {
-  __syncthreads();
-  sm[threadIdx.x] = v;
-  __syncthreads();
-  for (int s = 128; s > 0; s >>= 1) {
-    if ((int)threadIdx.x < s) sm[threadIdx.x] += sm[threadIdx.x + s];
-    __syncthreads();
-  }
-  return sm[0];
-}
-
 // Workgroup = Gaussian c, all in double.  stats != null: the M-step from (C, 1 + 2 D) statistics (every workgroup adds the C occupancies
 // and the C floored weights itself, by the same tree: the same bits everywhere); stats == null: the planes of the given w, mu, var.
 __global__ __launch_bounds__(256) void gmm_update_kernel(const double* __restrict__ stats, const double* __restrict__ w_in, double* __restrict__ w_out,
@@ -431,13 +401,13 @@ __global__ __launch_bounds__(256) void gmm_update_kernel(const double* __restric
   if (stats) {
     double part = 0.0;
     for (int i = tid; i < C; i += 256) part += stats[(long)i * NV];
-    const double ntot = iv_wg_sum(part, sm);
+    const double ntot = tv_wg_sum(part, sm);
     part = 0.0;
     for (int i = tid; i < C; i += 256) {
       const double n = stats[(long)i * NV], wi = n / ntot;
       part += (n < min_count || !(n > 0.0)) ? fmax(wi, min_weight) : wi;
     }
-    const double wtot = iv_wg_sum(part, sm);
+    const double wtot = tv_wg_sum(part, sm);
     const double n = stats[(long)c * NV];
     starved = n < min_count || !(n > 0.0);
     wc = (starved ? fmax(n / ntot, min_weight) : n / ntot) / wtot;
@@ -459,17 +429,17 @@ __global__ __launch_bounds__(256) void gmm_update_kernel(const double* __restric
     PB[(long)c * D + d] = (float)(-0.5 / v);
     part += log(6.283185307179586476925 * v) + m * m / v;
   }
-  const double q = iv_wg_sum(part, sm);
+  const double q = tv_wg_sum(part, sm);
   if (tid == 0) gc[c] = (float)(log(wc) - 0.5 * q);
 }
 
 // ---- launchers -------------------------------------------------------------------------------------------------------------------------
 int ivec_gselect_tile(int D, int C, size_t* lds_bytes) {
-  if (D < 1 || C < 1 || D > IV_MAX_D || C > IV_MAX_C) return 0;
+  if (D < 1 || C < 1 || D > IVEC_MAX_D || C > IVEC_MAX_C) return 0;
   const int DP = (D + 7) & ~7, LS = ((C + 15) & ~15) + 4, XS = 2 * DP + 4;
   for (int tf = 32; tf >= 16; tf >>= 1) {
     const size_t need = (size_t)tf * (LS + XS) * sizeof(float);
-    if (need <= IV_LDS_MAX) {
+    if (need <= TV_LDS_MAX) {
       if (lds_bytes) *lds_bytes = need;
       return tf;
     }
@@ -477,29 +447,19 @@ int ivec_gselect_tile(int D, int C, size_t* lds_bytes) {
   return 0;
 }
 
-// the kernels below take more than 64 KB of dynamic LDS: say so once per device
-static int iv_lds_limit() {
+static int iv_lds_limit() {               // the kernels below take more than 64 KB of dynamic LDS: say so once per device
   static std::atomic<int> done[64];
-  int dev = 0;
-  hipError_t e = hipGetDevice(&dev);
-  if (e != hipSuccess) return ssv_fail(-(int)e, "ivector: hipGetDevice: %s", hipGetErrorString(e));
-  if (dev >= 0 && dev < 64 && done[dev].load(std::memory_order_acquire)) return 0;
   const void* ks[5] = {(const void*)gmm_gselect_kernel<1>, (const void*)gmm_gselect_kernel<2>, (const void*)gmm_stats_kernel<4>,
                        (const void*)gmm_stats_kernel<12>, (const void*)gmm_stats_kernel<ST_MAXB>};
-  for (int i = 0; i < 5; ++i) {
-    e = hipFuncSetAttribute(ks[i], hipFuncAttributeMaxDynamicSharedMemorySize, IV_LDS_MAX);
-    if (e != hipSuccess) return ssv_fail(-(int)e, "ivector: hipFuncSetAttribute(MaxDynamicSharedMemorySize): %s", hipGetErrorString(e));
-  }
-  if (dev >= 0 && dev < 64) done[dev].store(1, std::memory_order_release);
-  return 0;
+  return tv_lds_limit_set(done, ks, 5, "ivector");
 }
 
 int ivec_launch_gselect(const float* X, const float* A, const float* B, const float* g, int* idx, float* post, float* loglik, long F, int D, int C, int nsel,
                         float min_post, hipStream_t st) {
   size_t lds = 0;
   const int tf = ivec_gselect_tile(D, C, &lds);
-  SSV_CHECK(tf > 0 && nsel <= IV_MAX_NSEL, SSV_UNSUPPORTED, "gmm_diag_gselect: D=%d (at most %d), C=%d (at most %d) or nsel=%d (at most %d) beyond the tiles", D, IV_MAX_D,
-            C, IV_MAX_C, nsel, IV_MAX_NSEL);
+  SSV_CHECK(tf > 0 && nsel <= IVEC_MAX_NSEL, SSV_UNSUPPORTED, "gmm_diag_gselect: D=%d (at most %d), C=%d (at most %d) or nsel=%d (at most %d) beyond the tiles", D, IVEC_MAX_D,
+            C, IVEC_MAX_C, nsel, IVEC_MAX_NSEL);
   SSV_CHECK((F + tf - 1) / tf <= 0x7fffffffL, SSV_UNSUPPORTED, "gmm_diag_gselect: %ld frames exceed the grid", F);
   SSV_TRY(iv_lds_limit());
   const int DP = (D + 7) & ~7, LS = ((C + 15) & ~15) + 4;
@@ -511,8 +471,8 @@ int ivec_launch_gselect(const float* X, const float* A, const float* B, const fl
 
 int ivec_launch_stats(const float* X, const int* idx, const float* post, const long* seg_off, float* slab, long F, int D, int C, int nsel, int S, int order,
                       hipStream_t st) {
-  SSV_CHECK(D <= IV_MAX_D && C <= IV_MAX_C && nsel <= IV_MAX_NSEL, SSV_UNSUPPORTED, "gmm_diag_stats: D=%d (at most %d), C=%d (at most %d) or nsel=%d (at most %d) beyond the tiles",
-            D, IV_MAX_D, C, IV_MAX_C, nsel, IV_MAX_NSEL);
+  SSV_CHECK(D <= IVEC_MAX_D && C <= IVEC_MAX_C && nsel <= IVEC_MAX_NSEL, SSV_UNSUPPORTED, "gmm_diag_stats: D=%d (at most %d), C=%d (at most %d) or nsel=%d (at most %d) beyond the tiles",
+            D, IVEC_MAX_D, C, IVEC_MAX_C, nsel, IVEC_MAX_NSEL);
   const int NV = 1 + order * D, nvb = (NV + 15) >> 4, VS = nvb * 16 + 4, gtiles = ssv_cdiv(C, ST_TG);
   SSV_CHECK((long)S * gtiles <= 0x7fffffffL, SSV_UNSUPPORTED, "gmm_diag_stats: %d segments x %d Gaussian tiles exceed the grid", S, gtiles);
   const size_t lds = ((size_t)ST_TG * ST_GS + (size_t)ST_TF * VS) * sizeof(float);

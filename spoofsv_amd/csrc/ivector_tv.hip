@@ -1,39 +1,24 @@
 // The middle of the i-vector system on the device (include/ssv_hip.h, "I-vector extractor"), gfx950: the planes of a total-variability
-// matrix, the exact-fp32 product family that builds every utterance's posterior precision and linear term (and, transposed, the
+// matrix, the exact-fp32 product family (the tile of exact_product.h) that builds every utterance's posterior precision and linear term (and, transposed, the
 // M-step's accumulators), the per-utterance E-step and the per-Gaussian M-step -- both a Cholesky factorisation, inverse and solve of a
 // packed lower triangle held in LDS, in double -- the centring of the first-order statistics, and cosine trial scoring.
 // The model is OURS, stated at the entries; Kaldi's ivector-extractor-* binaries are not reproduced.
 // Arithmetic is independent of ssv_set_precision.  No float atomics; the order of every sum follows from the shapes alone.
 // This file holds the kernels and their launchers (-2 for a shape beyond them); api_ivector.hip holds the entries and the checks (-1).
-#include "tv_triangle.h"          // tv_tri, tv_wave_sum, tv_cholesky, tv_trtri, tv_lauum, TV_MAX_R, TV_LDS_MAX, tv_lds_limit_set
+#include <type_traits>
+#include "tv_triangle.h"          // tv_tri, tv_wave_sum, tv_cholesky, tv_trtri, tv_lauum, TV_LDS_MAX, tv_lds_limit_set; the limits and launchers (ivec_chain.h)
+#include "exact_product.h"        // xp_tile, its maps and constants, xp_grid
 
-#define TV_MAX_C 2048
-#define TV_MAX_D 128
-#define TV_TILE 64                  // products: a workgroup owns a 64 x 64 tile of the output, a wave a 32 x 32 quarter of it
-#define TV_KS 32                    // K elements staged per step
-#define TV_LS (TV_TILE + 1)         // row stride of a staged step (k-major): the transposing store of the plain form hits 32 banks
-#define TV_RUN 256                  // K elements of one fp32 chain; the runs are added in double (ssv_ivec_product_run)
 #define TV_ES_THREADS 1024          // E-step: 16 waves, four per SIMD -- the triangle allows one workgroup a CU, so its waves are the occupancy
 #define TV_UP_THREADS 512           // M-step: 8 waves (a right-hand side per wave; the waves' solution rows share the LDS left by the triangle)
 #define TV_COS_THREADS 256
-
-#pragma GCC visibility push(hidden)      // the launchers: called by api_ivector.hip (which repeats these lines), not exported
-int tv_launch_planes(const double* T, const double* var, float* G, float* Pk, int C, int D, int R, hipStream_t st);
-int tv_launch_centre(const float* N, const float* F, const double* mu, float* Ft, long U, int C, int D, hipStream_t st);
-int tv_launch_product(const float* A, const float* B, float* out, long m, long n, long K, hipStream_t st);
-int tv_launch_product_tn(const float* A, const float* B, double* acc, long U, long m, long n, hipStream_t st);
-int tv_launch_estep(const float* Lp, const float* b, float* w, float* M, double* obj, long U, int R, hipStream_t st);
-int tv_launch_update(const double* A, const double* Cm, const double* Nc, const double* J, double* T, int C, int D, int R, double min_count, hipStream_t st);
-int tv_launch_cosine(const float* enroll, const long* spk_off, const float* evalv, float* scores, long n_enroll, int S, long E, int R, hipStream_t st);
-#pragma GCC visibility pop
-
 
 // ---- planes ------------------------------------------------------------------------------------------------------------------------------
 // Workgroup = Gaussian c.  G_c = diag(1 / var_c) T_c and the packed lower triangle of Pk_c = T_c^T G_c, summed over d in double in
 // ascending d and rounded once.
 __global__ __launch_bounds__(256) void tv_planes_kernel(const double* __restrict__ T, const double* __restrict__ var, float* __restrict__ G,
                                                         float* __restrict__ Pk, int D, int R, int P) {
-  __shared__ double iv[TV_MAX_D];
+  __shared__ double iv[IVEC_MAX_D];
   const int c = blockIdx.x, tid = threadIdx.x;
   const double* Tc = T + (long)c * D * R;
   const double* vc = var + (long)c * D;
@@ -59,89 +44,23 @@ __global__ __launch_bounds__(256) void tv_centre_kernel(const float* __restrict_
 }
 
 // ---- the product family ------------------------------------------------------------------------------------------------------------------
-// out (m, n) = A B on v_mfma_f32_16x16x4_f32, B (K, n) row-major; TR = false: A (m, K) row-major, out float32, rounded once;
-// TR = true: A (K, m) row-major (the product is A^T B) and the result is ADDED to float64 accumulators.  Workgroup = one 64 x 64 tile of
-// the output (every element has one owner), wave = a 32 x 32 quarter.  K is walked in steps of TV_KS staged k-major in LDS (zeros
-// beyond an edge); the step after the one being multiplied waits in registers.  An fp32 chain runs over TV_RUN elements of K from zero
-// accumulators and is then added to DOUBLE registers.  The order of an element's sum depends on K alone: a row of the output does
-// not depend on the rows that share its launch.
+// out (m, n) = A B on the tile of exact_product.h, which states the order of the sums; B (K, n) row-major.  TR = false: A (m, K) row-major,
+// out float32, rounded once; TR = true: A (K, m) row-major (the product is A^T B) and the result is ADDED to float64 accumulators.
+// Workgroup = one tile of the output: every element has one owner.
 template <bool TR>
 __global__ __launch_bounds__(256) void tv_product_kernel(const float* __restrict__ A, const float* __restrict__ B, float* __restrict__ out,
                                                          double* __restrict__ acc_out, long m, long n, long K) {
-  __shared__ float As[TV_KS * TV_LS], Bs[TV_KS * TV_LS];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, kq = lane >> 4, cq = lane & 15;
-  const long m0 = (long)blockIdx.y * TV_TILE, n0 = (long)blockIdx.x * TV_TILE;
-  const int wm = (wave >> 1) * 32, wn = (wave & 1) * 32;
-  float ra[8], rb[8];
-  auto fetch = [&](long k0) {
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      if (TR) {
-        const long k = k0 + (tid >> 6) + 4 * i, r = m0 + (tid & 63);
-        ra[i] = (k < K && r < m) ? A[k * m + r] : 0.f;
-      } else {
-        const long k = k0 + (tid & 31), r = m0 + (tid >> 5) + 8 * i;
-        ra[i] = (k < K && r < m) ? A[r * K + k] : 0.f;
-      }
-      const long k = k0 + (tid >> 6) + 4 * i, c = n0 + (tid & 63);
-      rb[i] = (k < K && c < n) ? B[k * n + c] : 0.f;
+  const long m0 = (long)blockIdx.y * XP_TILE, n0 = (long)blockIdx.x * XP_TILE;
+  auto load_a = [&](long k, int r) { return (k < K && m0 + r < m) ? (TR ? A[k * m + m0 + r] : A[(m0 + r) * K + k]) : 0.f; };
+  auto load_b = [&](long k, int c) { return (k < K && n0 + c < n) ? B[k * n + n0 + c] : 0.f; };
+  auto store = [&](int r, int c, double v) {
+    const long row = m0 + r, col = n0 + c;
+    if (row < m && col < n) {
+      if (TR) acc_out[row * n + col] += v;
+      else out[row * n + col] = (float)v;
     }
   };
-  double sum[2][2][4];
-  f32x4 acc[2][2];
-#pragma unroll
-  for (int bi = 0; bi < 2; ++bi)
-#pragma unroll
-    for (int bj = 0; bj < 2; ++bj) {
-      acc[bi][bj] = (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int r = 0; r < 4; ++r) sum[bi][bj][r] = 0.0;
-    }
-  const long nst = (K + TV_KS - 1) / TV_KS;
-  fetch(0);
-  for (long s = 0; s < nst; ++s) {
-    __syncthreads();                      // the previous step's MFMAs have read As and Bs
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      if (TR) As[((tid >> 6) + 4 * i) * TV_LS + (tid & 63)] = ra[i];
-      else As[(tid & 31) * TV_LS + (tid >> 5) + 8 * i] = ra[i];
-      Bs[((tid >> 6) + 4 * i) * TV_LS + (tid & 63)] = rb[i];
-    }
-    __syncthreads();
-    if (s + 1 < nst) fetch((s + 1) * TV_KS);
-#pragma unroll
-    for (int q = 0; q < TV_KS / 4; ++q) {
-      const int kk = (q * 4 + kq) * TV_LS;
-      const float a0 = As[kk + wm + cq], a1 = As[kk + wm + 16 + cq], b0 = Bs[kk + wn + cq], b1 = Bs[kk + wn + 16 + cq];
-      acc[0][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0, b0, acc[0][0], 0, 0, 0);
-      acc[0][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0, b1, acc[0][1], 0, 0, 0);
-      acc[1][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1, b0, acc[1][0], 0, 0, 0);
-      acc[1][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1, b1, acc[1][1], 0, 0, 0);
-    }
-    if ((s + 1) % (TV_RUN / TV_KS) == 0 || s + 1 == nst) {
-#pragma unroll
-      for (int bi = 0; bi < 2; ++bi)
-#pragma unroll
-        for (int bj = 0; bj < 2; ++bj) {
-#pragma unroll
-          for (int r = 0; r < 4; ++r) sum[bi][bj][r] += (double)acc[bi][bj][r];
-          acc[bi][bj] = (f32x4){0.f, 0.f, 0.f, 0.f};
-        }
-    }
-  }
-  // C/D layout: column = lane & 15, row = (lane >> 4) * 4 + r
-#pragma unroll
-  for (int bi = 0; bi < 2; ++bi)
-#pragma unroll
-    for (int bj = 0; bj < 2; ++bj)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const long row = m0 + wm + bi * 16 + kq * 4 + r, col = n0 + wn + bj * 16 + cq;
-        if (row < m && col < n) {
-          if (TR) acc_out[row * n + col] += sum[bi][bj][r];
-          else out[row * n + col] = (float)sum[bi][bj][r];
-        }
-      }
+  xp_tile<typename std::conditional<TR, XpRowFast, XpKFast>::type, XpRowFast>(K, load_a, load_b, store);
 }
 
 // ---- E-step ------------------------------------------------------------------------------------------------------------------------------
@@ -324,8 +243,8 @@ static int tv_lds_limit() {               // the kernels below take more than 64
 }
 
 static int tv_shape_ok(const char* what, int C, int D, int R) {
-  SSV_CHECK(R <= TV_MAX_R && C <= TV_MAX_C && D <= TV_MAX_D, SSV_UNSUPPORTED, "%s: R=%d (at most %d), C=%d (at most %d) or D=%d (at most %d) beyond the kernels", what, R,
-            TV_MAX_R, C, TV_MAX_C, D, TV_MAX_D);
+  SSV_CHECK(R <= IVEC_MAX_R && C <= IVEC_MAX_C && D <= IVEC_MAX_D, SSV_UNSUPPORTED, "%s: R=%d (at most %d), C=%d (at most %d) or D=%d (at most %d) beyond the kernels", what, R,
+            IVEC_MAX_R, C, IVEC_MAX_C, D, IVEC_MAX_D);
   return 0;
 }
 
@@ -343,23 +262,16 @@ int tv_launch_centre(const float* N, const float* F, const double* mu, float* Ft
   return ssv_check_launch("ivec_centre_stats");
 }
 
-static int tv_product_grid(const char* what, long m, long n, dim3* grid) {
-  const long gx = (n + TV_TILE - 1) / TV_TILE, gy = (m + TV_TILE - 1) / TV_TILE;
-  SSV_CHECK(gx <= 0x7fffffffL && gy <= 65535, SSV_UNSUPPORTED, "%s: %ld x %ld tiles exceed the grid (2^31 - 1 x 65535)", what, gx, gy);
-  *grid = dim3((unsigned)gx, (unsigned)gy);
-  return 0;
-}
-
 int tv_launch_product(const float* A, const float* B, float* out, long m, long n, long K, hipStream_t st) {
   dim3 grid;
-  SSV_TRY(tv_product_grid("ivec_product", m, n, &grid));
+  SSV_TRY(xp_grid("ivec_product", m, n, &grid));
   hipLaunchKernelGGL(tv_product_kernel<false>, grid, dim3(256), 0, st, A, B, out, (double*)nullptr, m, n, K);
   return ssv_check_launch("ivec_product");
 }
 
 int tv_launch_product_tn(const float* A, const float* B, double* acc, long U, long m, long n, hipStream_t st) {
   dim3 grid;
-  SSV_TRY(tv_product_grid("ivec_product_tn", m, n, &grid));
+  SSV_TRY(xp_grid("ivec_product_tn", m, n, &grid));
   hipLaunchKernelGGL(tv_product_kernel<true>, grid, dim3(256), 0, st, A, B, (float*)nullptr, acc, m, n, U);
   return ssv_check_launch("ivec_product_tn");
 }

@@ -1,39 +1,20 @@
 // The back end of the i-vector system on the device (include/ssv_hip.h, "I-vector back end: PLDA"), gfx950: class statistics of
 // length-normalised vectors, the float64 pieces of two-covariance PLDA's EM (inverses of packed triangles in LDS by the extractor's
 // three functions, the per-speaker posterior means, the weighted outer-product sums, the update and the objective), the transform's row
-// kernels, the speaker planes, and the score product [t^2, t] H^T + k on the exact-fp32 MFMA.
+// kernels, the speaker planes, and the score product [t^2, t] H^T + k on the exact-fp32 tile of exact_product.h.
 // The model is OURS, stated at the entries; Kaldi's ivector-compute-plda and ivector-plda-scoring are not reproduced.
 // Arithmetic is independent of ssv_set_precision.  No float atomics; the order of every sum follows from the shapes alone.
 // This file holds the kernels and their launchers (-2 for a shape beyond them); api_plda.hip holds the entries and the checks (-1).
-#include "tv_triangle.h"
+#include "tv_triangle.h"          // the packed triangle, tv_wave_sum, tv_lds_limit_set; IVEC_MAX_R and the launchers (ivec_chain.h)
+#include "exact_product.h"        // xp_tile, XpKFast, xp_grid
 
 #define PL_THREADS 256
 #define PL_INV_THREADS 512          // the inverse: 8 waves (the triangle allows one workgroup a CU)
 #define PL_CHUNK 256                // class statistics: rows whose factors wait in LDS at a time
 #define PL_SY_TILE 16               // wsyrk: a workgroup owns 16 x 16 elements of the output, a thread one
 #define PL_SY_ROWS 64               // wsyrk: rows of V staged per step
-#define PL_TILE 64                  // score: a workgroup owns a 64 x 64 tile, a wave a 32 x 32 quarter
-#define PL_KS 32                    // score: K elements staged per step
-#define PL_LS (PL_TILE + 1)
-#define PL_RUN 256                  // score: K elements of one fp32 chain; the runs are added in double
 
-#pragma GCC visibility push(hidden)      // the launchers: called by api_plda.hip (which repeats these lines), not exported
-int plda_launch_class_stats(const float* X, const long* spk_off, float* Xd, double* means, double* mu, float* model, long n, int S, int R, int length_norm,
-                            hipStream_t st);
-int plda_launch_mixed_inverse(const double* a, const double* b, long b_stride, const double* coef, double* out, double* logdet, int J, int R, hipStream_t st);
-int plda_launch_em_classes(const double* means, const double* mu, const int* cnt, const int* cls, const double* Mx, const double* Winv, double* w, double* r,
-                           double* quad, int S, int R, int J, hipStream_t st);
-int plda_launch_wsyrk(const double* V, const double* c, double* acc, long S, int R, hipStream_t st);
-int plda_launch_em_update(const double* Mx, const double* ldMx, const double* nspk, const double* nrow, const double* WW, const double* RR, const double* Sigma,
-                          const double* Winv, const double* ldW, const double* ldB, const int* cnt, const int* cls, const double* quad, double* W, double* B,
-                          double* obj, int J, int S, int R, double Sn, double N, hipStream_t st);
-int plda_launch_centre(const float* X, const double* mu, float* Xc, long n, int R, int length_norm, hipStream_t st);
-int plda_launch_scale(float* U, const double* psi, const int* nex, int nex_all, long n, int R, hipStream_t st);
-int plda_launch_speaker_planes(const float* y, const int* nspk, const double* psi, float* H, double* k, int S, int R, hipStream_t st);
-int plda_launch_score(const float* T, const float* H, const double* k, float* scores, long E, long S, int R, hipStream_t st);
-#pragma GCC visibility pop
-
-// sum over R <= 192 of a per-element value held three to a lane (elements lane, lane + 64, lane + 128), then the butterfly
+// sum over R <= IVEC_MAX_R of a per-element value held three to a lane (elements lane, lane + 64, lane + 128), then the butterfly
 __device__ __forceinline__ double pl_row_ss(const float* __restrict__ row, int R, int lane) {
   double ss = 0.0;
 #pragma unroll
@@ -245,6 +226,7 @@ __global__ __launch_bounds__(PL_THREADS) void plda_em_update_kernel(const double
 }
 
 // the sum of 256 per-thread partial values: wave 0 adds four to a lane in ascending order, then the butterfly; every thread of wave 0 gets it
+// (not tv_wg_sum: that one's halving tree adds in another order, and these sums keep theirs)
 __device__ __forceinline__ double pl_block_sum(double* part, double v) {
   const int tid = threadIdx.x;
   __syncthreads();
@@ -345,84 +327,32 @@ __global__ __launch_bounds__(PL_THREADS) void plda_speaker_planes_kernel(const f
 }
 
 // ---- the score ---------------------------------------------------------------------------------------------------------------------------
-// scores (E, S) float32 = [t^2, t] H^T + k on v_mfma_f32_16x16x4_f32: T (E, R), H (S, 2 R) float32 row-major, k (S) float64.  Workgroup = one
-// 64 x 64 tile (every element has one owner), wave = a 32 x 32 quarter.  K = 2 R is walked in steps of PL_KS staged k-major in LDS (zeros
-// beyond an edge): element kk of the left operand is t[kk]^2 for kk < R (one float32 product, made as the eval tile is fetched) and t[kk - R]
-// beyond, so the (E, 2 R) array is never written; both operands are K-contiguous in memory.  The step after the one being multiplied waits in
-// registers.  An fp32 chain runs over PL_RUN elements of K from zero accumulators and is then added to DOUBLE registers; k is added in double
-// and the result rounded once.  The order of an element's sum depends on R alone: a row does not depend on the rows that share its launch.
+// scores (E, S) float32 = [t^2, t] H^T + k on the tile of exact_product.h, which states the order of the sums (K = 2 R): T (E, R),
+// H (S, 2 R) float32 row-major, k (S) float64.  Element kk of the left operand is t[kk]^2 for kk < R (one float32 product, made as the eval
+// tile is fetched) and t[kk - R] beyond, so the (E, 2 R) array is never written; both operands are K-contiguous in memory.  k is added in
+// double and the result rounded once.  Workgroup = one tile of the scores: every element has one owner.
 __global__ __launch_bounds__(256) void plda_score_kernel(const float* __restrict__ T, const float* __restrict__ H, const double* __restrict__ kv,
                                                          float* __restrict__ scores, long E, long S, int R) {
-  __shared__ float As[PL_KS * PL_LS], Bs[PL_KS * PL_LS];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, kq = lane >> 4, cq = lane & 15;
-  const long m0 = (long)blockIdx.y * PL_TILE, n0 = (long)blockIdx.x * PL_TILE;
-  const int wm = (wave >> 1) * 32, wn = (wave & 1) * 32, K = 2 * R;
-  float ra[8], rb[8];
-  auto fetch = [&](int k0) {
-    const int k = k0 + (tid & 31);
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      const long r = m0 + (tid >> 5) + 8 * i, c = n0 + (tid >> 5) + 8 * i;
-      float a = 0.f;
-      if (k < K && r < E) {
-        a = T[r * R + (k < R ? k : k - R)];
-        if (k < R) a = a * a;
-      }
-      ra[i] = a;
-      rb[i] = (k < K && c < S) ? H[c * K + k] : 0.f;
+  const long m0 = (long)blockIdx.y * XP_TILE, n0 = (long)blockIdx.x * XP_TILE;
+  const int K = 2 * R;
+  auto load_a = [&](long kl, int r) {
+    const int k = (int)kl;
+    float a = 0.f;
+    if (k < K && m0 + r < E) {
+      a = T[(m0 + r) * R + (k < R ? k : k - R)];
+      if (k < R) a = a * a;
     }
+    return a;
   };
-  double sum[2][2][4];
-  f32x4 acc[2][2];
-#pragma unroll
-  for (int bi = 0; bi < 2; ++bi)
-#pragma unroll
-    for (int bj = 0; bj < 2; ++bj) {
-      acc[bi][bj] = (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int r = 0; r < 4; ++r) sum[bi][bj][r] = 0.0;
-    }
-  const int nst = (K + PL_KS - 1) / PL_KS;
-  fetch(0);
-  for (int s = 0; s < nst; ++s) {
-    __syncthreads();                      // the previous step's MFMAs have read As and Bs
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      As[(tid & 31) * PL_LS + (tid >> 5) + 8 * i] = ra[i];
-      Bs[(tid & 31) * PL_LS + (tid >> 5) + 8 * i] = rb[i];
-    }
-    __syncthreads();
-    if (s + 1 < nst) fetch((s + 1) * PL_KS);
-#pragma unroll
-    for (int q = 0; q < PL_KS / 4; ++q) {
-      const int kk = (q * 4 + kq) * PL_LS;
-      const float a0 = As[kk + wm + cq], a1 = As[kk + wm + 16 + cq], b0 = Bs[kk + wn + cq], b1 = Bs[kk + wn + 16 + cq];
-      acc[0][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0, b0, acc[0][0], 0, 0, 0);
-      acc[0][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0, b1, acc[0][1], 0, 0, 0);
-      acc[1][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1, b0, acc[1][0], 0, 0, 0);
-      acc[1][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1, b1, acc[1][1], 0, 0, 0);
-    }
-    if ((s + 1) % (PL_RUN / PL_KS) == 0 || s + 1 == nst) {
-#pragma unroll
-      for (int bi = 0; bi < 2; ++bi)
-#pragma unroll
-        for (int bj = 0; bj < 2; ++bj) {
-#pragma unroll
-          for (int r = 0; r < 4; ++r) sum[bi][bj][r] += (double)acc[bi][bj][r];
-          acc[bi][bj] = (f32x4){0.f, 0.f, 0.f, 0.f};
-        }
-    }
-  }
-  // C/D layout: column = lane & 15, row = (lane >> 4) * 4 + r
-#pragma unroll
-  for (int bi = 0; bi < 2; ++bi)
-#pragma unroll
-    for (int bj = 0; bj < 2; ++bj)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const long row = m0 + wm + bi * 16 + kq * 4 + r, col = n0 + wn + bj * 16 + cq;
-        if (row < E && col < S) scores[row * S + col] = (float)(sum[bi][bj][r] + kv[col]);
-      }
+  auto load_b = [&](long kl, int c) {
+    const int k = (int)kl;
+    return (k < K && n0 + c < S) ? H[(n0 + c) * K + k] : 0.f;
+  };
+  auto store = [&](int r, int c, double v) {
+    const long row = m0 + r, col = n0 + c;
+    if (row < E && col < S) scores[row * S + col] = (float)(v + kv[col]);
+  };
+  xp_tile<XpKFast, XpKFast>(K, load_a, load_b, store);
 }
 
 // ---- launchers -------------------------------------------------------------------------------------------------------------------------
@@ -433,7 +363,7 @@ static int plda_lds_limit() {             // the inverse takes more than 64 KB o
 }
 
 static int plda_rank_ok(const char* what, int R) {
-  SSV_CHECK(R <= TV_MAX_R, SSV_UNSUPPORTED, "%s: R=%d (at most %d) beyond the kernels", what, R, TV_MAX_R);
+  SSV_CHECK(R <= IVEC_MAX_R, SSV_UNSUPPORTED, "%s: R=%d (at most %d) beyond the kernels", what, R, IVEC_MAX_R);
   return 0;
 }
 
@@ -516,8 +446,8 @@ int plda_launch_speaker_planes(const float* y, const int* nspk, const double* ps
 
 int plda_launch_score(const float* T, const float* H, const double* k, float* scores, long E, long S, int R, hipStream_t st) {
   SSV_TRY(plda_rank_ok("plda_score", R));
-  const long gx = (S + PL_TILE - 1) / PL_TILE, gy = (E + PL_TILE - 1) / PL_TILE;
-  SSV_CHECK(gx <= 0x7fffffffL && gy <= 65535, SSV_UNSUPPORTED, "plda_score: %ld x %ld tiles exceed the grid (2^31 - 1 x 65535)", gx, gy);
-  hipLaunchKernelGGL(plda_score_kernel, dim3((unsigned)gx, (unsigned)gy), dim3(256), 0, st, T, H, k, scores, E, S, R);
+  dim3 grid;
+  SSV_TRY(xp_grid("plda_score", E, S, &grid));
+  hipLaunchKernelGGL(plda_score_kernel, grid, dim3(256), 0, st, T, H, k, scores, E, S, R);
   return ssv_check_launch("plda_score");
 }

@@ -16,6 +16,16 @@ static inline size_t align256(size_t n) { return (n + 255) & ~(size_t)255; }
 static inline size_t zmax(size_t a, size_t b) { return a > b ? a : b; }
 static inline int pad32(int n) { return (n + 31) & ~31; }
 
+// The host copy of an offsets array (n + 1 entries, optional): [off[0], off[n]) must lie inside the `total` items and no entry descend.
+// `arg` names the array, `one` one of its intervals, `items` what they index: the words of the two messages.
+static inline int host_offsets_ok(const char* who, const char* arg, const char* one, const char* items, const long* off, int n, long total) {
+  if (!off) return 0;
+  SSV_CHECK(off[0] >= 0 && off[n] <= total, SSV_BAD_SHAPE, "%s: %ss [%ld, %ld) leave the %ld %s", who, one, off[0], off[n], total, items);
+  for (int i = 0; i < n; ++i)
+    SSV_CHECK(off[i] <= off[i + 1], SSV_BAD_SHAPE, "%s: %s descends at %s %d (%ld > %ld)", who, arg, one, i, off[i], off[i + 1]);
+  return 0;
+}
+
 // ---- workspace layout ------------------------------------------------------------------------------------------------
 // The regions of a workspace are taken in order, each from a 256-byte boundary; `off` after the last take is the size.  Every
 // workspace has ONE layout function built on this: the public *_workspace query returns its total and the entry point carves

@@ -1,17 +1,28 @@
 // The packed float64 triangle in LDS: Cholesky, triangular inverse and W^T W of a symmetric positive definite matrix, shared by the
-// i-vector extractor (ivector_tv.hip) and the PLDA back end (plda.hip), with the wave sum and the dynamic-LDS limit they both need.
+// i-vector extractor (ivector_tv.hip), the PLDA back end (plda.hip) and the full-covariance UBM (fgmm.hip), with the wave sum, the
+// workgroup sum and the dynamic-LDS limit that the chain's kernel files need (ivector.hip takes the last two).
 #pragma once
 #include <atomic>
-#include "ssv_common.h"
+#include "ivec_chain.h"             // IVEC_MAX_R: the largest triangle
 
-#define TV_MAX_R 192                // the packed float64 triangle of R = 192 is 148,224 bytes: it fits the 160 KiB LDS with the vectors
-#define TV_LDS_MAX (160 * 1024)
+#define TV_LDS_MAX (160 * 1024)     // LDS of a CU: one workgroup may take all of it
 
 __device__ __forceinline__ int tv_tri(int i, int j) { return i * (i + 1) / 2 + j; }       // packed lower triangle, row-major, j <= i
 __device__ __forceinline__ double tv_wave_sum(double v) {      // every lane gets the sum over the 64 lanes; the butterfly's shape is fixed
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
   return v;
+}
+// sum of a per-thread double over the 256 threads of a workgroup (sm: 256 doubles of LDS), every thread gets it; the tree's shape is fixed
+__device__ __forceinline__ double tv_wg_sum(double v, double* sm) {
+  __syncthreads();
+  sm[threadIdx.x] = v;
+  __syncthreads();
+  for (int s = 128; s > 0; s >>= 1) {
+    if ((int)threadIdx.x < s) sm[threadIdx.x] += sm[threadIdx.x + s];
+    __syncthreads();
+  }
+  return sm[0];
 }
 
 // ---- the packed triangle in LDS --------------------------------------------------------------------------------------------------------

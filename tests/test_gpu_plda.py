@@ -278,6 +278,22 @@ def test_speaker_planes_and_score(Rk, E, S):
         assert torch.equal(model.score_planes(H.t, k.t, tg[e:e + 1])[0], out.t[e])
 
 
+@pytest.mark.parametrize("Rk", (17, 129, 192))          # K = 2 R: two past a staged step of 32, two past a run of 256, the largest rank
+def test_score_is_the_product_tile(Rk):
+    """ssv_plda_score and ssv_ivec_product are ONE tile (csrc/exact_product.h): with k = 0 the score equals the plain product of
+    [t^2, t] (t^2 one float32 product, as the score's loader makes it) with H^T bit for bit -- the same values staged at the same LDS
+    positions, the same MFMA sequence, the folds into double at the same steps, and (float)(sum + 0.0) is (float)sum."""
+    E, S = 65, 63
+    t, y, n, psi = R.score_case(E, S, Rk)
+    tg, Hg, kg = _dev(t), _dev(R.planes(y, n, psi)[0].astype(np.float32)), torch.zeros(S, dtype=torch.float64, device=DEV)
+    score, prod = Guarded((E, S)), Guarded((E, S))
+    _call("ssv_plda_score", _p(tg), _p(Hg), _p(kg), _p(score.t), E, S, Rk, _st())
+    left, right = torch.cat([tg * tg, tg], 1).contiguous(), Hg.t().contiguous()
+    _call("ssv_ivec_product", _p(left), _p(right), _p(prod.t), E, S, 2 * Rk, _st())
+    assert score.intact() and prod.intact() and np.isfinite(score.numpy()).all() and np.abs(score.numpy()).max() > 0
+    assert np.array_equal(score.numpy().view(np.int32), prod.numpy().view(np.int32))
+
+
 # ================================================================================================ the model's file and the chain
 @functools.lru_cache(maxsize=None)
 def _chain():
